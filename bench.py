@@ -21,9 +21,16 @@ is built by the first (warm-up) query, its time reported as entry_cut_ms.  `one_
 build + first batch with the default (coarse) cut.  --dist runs every collective path at N = 1 too (the nccl process
 group, the broadcast unpacked on the source, both exchanges, the secondaries), as an 8-GPU node's ranks do.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--queries Q]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--queries Q] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
     python -m torch.distributed.run --nproc-per-node 1 ... bench.py --gpus 1 --dist
+
+A plain run does what `value` needs and no more: setup, W warm-up steps, K timed steps, and one result line with
+`value`, `ms_per_step`, the per-phase `breakdown_ms_per_step` of the timed steps (HIP events on their stream), the
+build and entry-cut times.  --dump-outputs DIR then writes the last timed step's answer (face, part, point; float64
+.npy, a fixed seeded sample of 2^20 rows of a larger answer) so that two builds can be compared output for output.
+Every other line described here (`value_without_allgather`, `value_narrow_exchange`, `value_weak_100M_per_gpu`, the
+C4 / C5 secondaries, `one_shot`, `roofline`, `cpu_baseline`) takes runs of its own and is measured only with --full.
 
 Rank 0 prints ONE JSON line.  `roofline` is for the traversal kernel (k_knn) on rank 0's shard: algorithmic
 bytes per launch = S_rank * (56 + 64 * nodes/query + 80 * leaves/query) with the per-query
@@ -72,7 +79,7 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--queries", type=int, default=100_000_000,
                     help="queries per step: one C3 stream, sharded contiguously over the GPUs")
-    ap.add_argument("--no-weak", action="store_true", help="N > 1: skip the weak-scaling (100M per GPU) line")
+    ap.add_argument("--no-weak", action="store_true", help="--full, N > 1: skip the weak-scaling (100M per GPU) line")
     ap.add_argument("--freq", type=int, default=224, help="icosphere frequency (224 -> 1,003,520 faces)")
     ap.add_argument("--cpu-queries", type=int, default=24000,
                     help="CPU baseline: fixed sample of queries per host thread (1 thread: ~12 s)")
@@ -81,13 +88,22 @@ def parse():
                     help="skip the one-shot line (profiling runs: its fresh tree's traversals would mix into the kernel "
                          "statistics of the timed one)")
     ap.add_argument("--secondary", choices=("auto", "on", "off"), default="auto",
-                    help="C5 visibility and C4 batch lines beside value (auto: when the collective path runs, the "
-                         "configs north_star shards across GPUs)")
+                    help="--full: C5 visibility and C4 batch lines beside value (auto: when the collective path runs, "
+                         "the configs north_star shards across GPUs)")
     ap.add_argument("--dist", action="store_true",
                     help="the collective path at any N, N = 1 included: the nccl (RCCL) process group, the tree's "
                          "RCCL broadcast unpacked on every rank (the source too), the ResultRing all-gathers, the "
                          "no-allgather / weak lines and the sharded C4 / C5 secondaries.  Launch under "
                          "torch.distributed.run (a plain launch gets a one-rank rendezvous on 127.0.0.1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the answer of the last timed step (what a caller of the timed "
+                         "path receives) as DIR/face.npy, DIR/part.npy, DIR/point.npy (float64): every row, or a fixed "
+                         "seeded sample of DUMP_ROWS rows of a larger answer")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: everything else the benchmark measures (the one-shot line, the roofline "
+                         "from an instrumented traversal, the CPU baselines, and with the collective path the "
+                         "no-allgather / narrow-exchange / weak-scaling lines and the C4 / C5 secondaries); "
+                         "--no-cpu, --no-one-shot, --no-weak and --secondary select among these")
     return ap.parse_args()
 
 
@@ -234,6 +250,88 @@ def load_traffic(workload, S, build_id):
     return d, None
 
 
+def traversal_counts(tree, q, S_loc):
+    """The instrumented traversal of the shard's S_loc queries (a pass of its own, untimed): nodes and leaves
+    visited per query, with the tree's node and leaf sizes -> (n_node, n_leaf, node_bytes, leaf_bytes)."""
+    from mesh_amd import _native
+    nodes, leaves = _native.ctypes.c_uint64(0), _native.ctypes.c_uint64(0)
+    _native.check(_native.lib().msh_tree_nearest_stats(tree.ptr, q.data_ptr(), S_loc, _native.ctypes.byref(nodes),
+                                                        _native.ctypes.byref(leaves)))
+    info = tree.info()
+    return nodes.value / S_loc, leaves.value / S_loc, int(info.node_bytes), int(info.leaf_bytes)
+
+
+def roofline(counts, S_loc, avg_kernel_s, workload, S, world, build_id):
+    """The `roofline` object of the result line (--full): the traversal kernel's algorithmic bytes per launch from
+    traversal_counts, over its average duration in the timed region (HIP events), with the PMC record of the same
+    build where there is one."""
+    n_node, n_leaf, node_b, leaf_b = counts
+    # bytes the traversal requests per query with this layout (node_b-B nodes, leaf_b-B leaves), and the
+    # same counts priced with SURVEY §8(d)'s 64-B node model
+    bytes_per_query = 56 + node_b * n_node + leaf_b * n_leaf
+    bytes_per_query_s8d = 56 + 64 * n_node + 80 * n_leaf
+    achieved = S_loc * bytes_per_query / avg_kernel_s / 1e9
+    achieved_s8d = S_loc * bytes_per_query_s8d / avg_kernel_s / 1e9
+    tr, tr_reason = load_traffic(workload, S, build_id) if world == 1 else (None, "PMC profiles are of the N = 1 run")
+    traffic = tr.get("bytes_per_launch") if tr else None
+    return {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+            "kernel": "k_knn<0,false,true,true> + k_knn_coop<0,false> (pass 1 + pass 2: traversal + fp64 refinement)",
+            "kernel_ms": avg_kernel_s * 1e3, "queries_per_launch": S_loc, "bytes_per_query": bytes_per_query,
+            "node_bytes": node_b, "leaf_bytes": leaf_b,
+            "nodes_per_query": n_node, "leaves_per_query": n_leaf,
+            "s8d_64B_nodes": {"bytes_per_query": bytes_per_query_s8d, "achieved": achieved_s8d,
+                              "frac": achieved_s8d / HBM_PEAK_GBS},
+            "measured": ({"hbm_GBps": tr["bytes_per_launch"] / avg_kernel_s / 1e9,
+                          "l2_hit_rate": tr.get("l2_hit_rate"), "code": tr.get("code"),
+                          "build_id": tr.get("build_id"), "pmc_traversal_ms": tr.get("traversal_ms"),
+                          "isa": tr.get("isa")}
+                         if tr else None),
+            "traffic_note": tr_reason,
+            # the §8(d) byte model prices every node and leaf read as an HBM transfer; L2 and the
+            # Infinity Cache serve most of them (measured.hbm_GBps), so the model's rate can pass the peak
+            "frac_note": ("above 1: the §8(d) model counts cache-served node and leaf re-reads as HBM bytes; "
+                          "the fabric traffic is `measured`, and the kernel is bound by instruction issue "
+                          "and dependent-load latency (`latency`)") if achieved > HBM_PEAK_GBS else None,
+            # two more ceilings for the same kernel (the HBM `frac` above prices cache-served re-reads as HBM
+            # bytes): the algorithmic bytes against the aggregate L2 rate over the 8 XCDs (L2_PEAK_GBS), and the
+            # VALU pipe's busy fraction from the same build's SQ counters (wave-cycles issuing VALU x resident
+            # waves per SIMD)
+            "l2": achieved / L2_PEAK_GBS,
+            "l2_peak": L2_PEAK_GBS,
+            "issue": issue_frac(tr),
+            "issue_note": "SQ_ACTIVE_INST_VALU / SQ_WAVE_CYCLES of k_knn x resident waves per SIMD (from its "
+                          "VGPR and LDS use; profiles/pmc_traffic.json at the same build id)" if tr else None,
+            # latency side: what bounds the kernel (node steps issued per second, live; lane occupancy and
+            # memory waits from the same build's SQ counters)
+            "latency": {"node_steps_per_s": S_loc * n_node / avg_kernel_s,
+                        "leaf_tests_per_s": S_loc * n_leaf / avg_kernel_s,
+                        "lanes_active_valu": tr.get("lanes_active_valu") if tr else None,
+                        "wave_cycles_waiting_frac": tr.get("wave_cycles_waiting_frac") if tr else None,
+                        "wave_cycles_valu_frac": tr.get("wave_cycles_valu_frac") if tr else None}}
+
+
+DUMP_ROWS = 1 << 20  # rows of a --dump-outputs sample: 3 arrays, 5 float64 columns -> 40 MiB
+DUMP_SEED = 0
+
+
+def dump_outputs(path, face, part, point):
+    """--dump-outputs: the (face, part, point) answer of the last timed step as float64 .npy files.  An answer of
+    more than DUMP_ROWS rows is sampled at DUMP_ROWS distinct rows drawn once from a seeded generator (ascending;
+    a function of the row count only), so two builds run with the same arguments write the same rows."""
+    import torch
+    n = int(face.shape[0])
+    if n > DUMP_ROWS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False, shuffle=False))
+        sel = torch.from_numpy(idx).to(face.device)
+        face, part, point = face[sel], part[sel], point[sel]
+    os.makedirs(path, exist_ok=True)
+    # face and part are uint32 values carried in int32 tensors (NO_FACE = 0xFFFFFFFF); float64 holds them exactly
+    np.save(os.path.join(path, "face.npy"), face.cpu().numpy().view(np.uint32).astype(np.float64))
+    np.save(os.path.join(path, "part.npy"), part.cpu().numpy().view(np.uint32).astype(np.float64))
+    np.save(os.path.join(path, "point.npy"), np.ascontiguousarray(point.cpu().numpy(), dtype=np.float64))
+
+
 def main():
     args = parse()
     import torch
@@ -256,7 +354,8 @@ def main():
         dist.init_process_group("nccl", device_id=dev)
 
     from mesh_amd import _native, spatialsearch
-    from mesh_amd.distributed import NarrowRing, ResultRing, nearest_device, points_from_faces_device, replicate_tree
+    from mesh_amd.distributed import (NarrowRing, ResultRing, nearest_device, points_from_faces_device, replicate_tree,
+                                      shard_range)
     import workloads as W
 
     _native.set_device(local)
@@ -355,13 +454,25 @@ def main():
     g_ms, g_n = _native.timing_get("gather")
     u_ms, u_n = _native.timing_get("unpermute")
 
-    # ---- N > 1, reported beside value (never as value): the same steps without the exchange, with the narrow
+    # ---- --dump-outputs: the last timed step's answer, before anything below reuses its buffers (with the exchange:
+    # the gathered answer of the whole stream, as every rank holds it) ----
+    if args.dump_outputs and rank == 0:
+        if ring is None:
+            last = tuple(x[:S_loc] for x in slabs[0])
+        else:
+            last = ring.result((ring.k - 1) & 1)
+            if world * rows != S:  # unequal shards: drop the slabs' unanswered tail rows, leaving the S stream rows
+                spans = [shard_range(S, r, world) for r in range(world)]
+                last = tuple(torch.cat([x[r * rows:r * rows + b - a] for r, (a, b) in enumerate(spans)]) for x in last)
+        dump_outputs(args.dump_outputs, *last)
+
+    # ---- --full, N > 1, reported beside value (never as value): the same steps without the exchange, with the narrow
     # exchange (faces only, the other ranks' points rebuilt locally: NarrowRing), and the weak-scaling line (every
     # rank answers the whole stream; the world x S answers are all-gathered) ----
     elapsed_no_ag = elapsed_weak = elapsed_narrow = None
     probe = None
     errors = {}
-    if coll:
+    if coll and args.full:
         elapsed_no_ag = timed(lambda: answer(slabs[0]), args.steps)
         if S % world == 0:
             try:  # a line beside value: a failure is reported, not fatal to the value line
@@ -418,7 +529,7 @@ def main():
     # one-shot device caller (untimed for value): a fresh tree from the host mesh, its first 100M-row batch with the
     # automatic entry cut (the coarse grid, built by that call), results in HBM -- build + cut + batch
     one_shot = None
-    if world == 1 and not args.no_one_shot:
+    if args.full and world == 1 and not args.no_one_shot:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         t1 = spatialsearch.aabbtree_compute(v, f)
@@ -434,37 +545,22 @@ def main():
         del t1
 
     sec = None
-    if args.secondary == "on" or (args.secondary == "auto" and coll):
+    if args.full and (args.secondary == "on" or (args.secondary == "auto" and coll)):
         try:  # lines beside value: a failure is reported, not fatal to the value line
             sec = secondary(timed, world, rank, dev, args.steps, coll)
         except Exception as e:  # noqa: BLE001
             errors["secondary"] = "%s: %s" % (type(e).__name__, e)
             torch.cuda.empty_cache()
 
-    # ---- instrumented traversal (untimed): algorithmic bytes of this rank's shard ----
-    nodes, leaves = _native.ctypes.c_uint64(0), _native.ctypes.c_uint64(0)
-    _native.check(_native.lib().msh_tree_nearest_stats(tree.ptr, q.data_ptr(), S_loc, _native.ctypes.byref(nodes),
-                                                        _native.ctypes.byref(leaves)))
-    n_node = nodes.value / S_loc
-    n_leaf = leaves.value / S_loc
-    info = tree.info()
-    node_b, leaf_b = int(info.node_bytes), int(info.leaf_bytes)
-    # bytes the traversal requests per query with this layout (node_b-B nodes, leaf_b-B leaves), and the
-    # same counts priced with SURVEY §8(d)'s 64-B node model
-    bytes_per_query = 56 + node_b * n_node + leaf_b * n_leaf
-    bytes_per_query_s8d = 56 + 64 * n_node + 80 * n_leaf
+    # ---- --full: instrumented traversal (untimed, a pass of its own): algorithmic bytes of this rank's shard ----
+    counts = traversal_counts(tree, q, S_loc) if args.full else None
 
     if rank != 0:
         if coll:
             dist.barrier()
             dist.destroy_process_group()
         return
-    avg_kernel_s = (k_ms / max(k_n, 1)) / 1e3
-    achieved = S_loc * bytes_per_query / avg_kernel_s / 1e9
-    achieved_s8d = S_loc * bytes_per_query_s8d / avg_kernel_s / 1e9
     build_id = _native.build_id()
-    tr, tr_reason = load_traffic(workload, S, build_id) if world == 1 else (None, "PMC profiles are of the N = 1 run")
-    traffic = tr.get("bytes_per_launch") if tr else None
     total_q = S * args.steps
     out = {
         "metric": METRIC,
@@ -482,41 +578,9 @@ def main():
         "config": {"workload": workload, "faces": T, "queries_total": S, "queries_per_gpu": S_loc,
                    "parallelism": "dp%d (one query stream sharded contiguously per GPU, BVH replicated by RCCL "
                                   "broadcast, answers all-gathered)" % world},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     "kernel": "k_knn<0,false,true,true> + k_knn_coop<0,false> (pass 1 + pass 2: traversal + fp64 refinement)",
-                     "kernel_ms": avg_kernel_s * 1e3, "queries_per_launch": S_loc, "bytes_per_query": bytes_per_query,
-                     "node_bytes": node_b, "leaf_bytes": leaf_b,
-                     "nodes_per_query": n_node, "leaves_per_query": n_leaf,
-                     "s8d_64B_nodes": {"bytes_per_query": bytes_per_query_s8d, "achieved": achieved_s8d,
-                                       "frac": achieved_s8d / HBM_PEAK_GBS},
-                     "measured": ({"hbm_GBps": tr["bytes_per_launch"] / avg_kernel_s / 1e9,
-                                   "l2_hit_rate": tr.get("l2_hit_rate"), "code": tr.get("code"),
-                                   "build_id": tr.get("build_id"), "pmc_traversal_ms": tr.get("traversal_ms"),
-                                   "isa": tr.get("isa")}
-                                  if tr else None),
-                     "traffic_note": tr_reason,
-                     # the §8(d) byte model prices every node and leaf read as an HBM transfer; L2 and the
-                     # Infinity Cache serve most of them (measured.hbm_GBps), so the model's rate can pass the peak
-                     "frac_note": ("above 1: the §8(d) model counts cache-served node and leaf re-reads as HBM bytes; "
-                                   "the fabric traffic is `measured`, and the kernel is bound by instruction issue "
-                                   "and dependent-load latency (`latency`)") if achieved > HBM_PEAK_GBS else None,
-                     # latency side: what bounds the kernel (node steps issued per second, live; lane
-                     # occupancy and memory waits from the same build's SQ counters)
-                     # two more ceilings for the same kernel (the HBM `frac` above prices cache-served re-reads as
-                     # HBM bytes): the algorithmic bytes against the aggregate L2 rate (MI355X_MICROARCH.md §L2,
-                     # ~34.5 TB/s), and the VALU pipe's busy fraction from the same build's SQ counters
-                     # (wave-cycles issuing VALU x resident waves per SIMD)
-                     "l2": achieved / L2_PEAK_GBS,
-                     "l2_peak": L2_PEAK_GBS,
-                     "issue": issue_frac(tr),
-                     "issue_note": "SQ_ACTIVE_INST_VALU / SQ_WAVE_CYCLES of k_knn x resident waves per SIMD (from its "
-                                   "VGPR and LDS use; profiles/pmc_traffic.json at the same build id)" if tr else None,
-                     "latency": {"node_steps_per_s": S_loc * n_node / avg_kernel_s,
-                                 "leaf_tests_per_s": S_loc * n_leaf / avg_kernel_s,
-                                 "lanes_active_valu": tr.get("lanes_active_valu") if tr else None,
-                                 "wave_cycles_waiting_frac": tr.get("wave_cycles_waiting_frac") if tr else None,
-                                 "wave_cycles_valu_frac": tr.get("wave_cycles_valu_frac") if tr else None}},
+        # --full only: it needs the instrumented traversal's counts
+        "roofline": (roofline(counts, S_loc, (k_ms / max(k_n, 1)) / 1e3, workload, S, world, build_id)
+                     if counts is not None else None),
         "breakdown_ms_per_step": {"traversal": k_ms / max(k_n, 1), "pass1": p1_ms / max(p1_n, 1),
                                   "pass1_superleaders": sl_ms / max(sl_n, 1),
                                   "pass1_leaders": ld_ms / max(ld_n, 1), "pass1_followers": fl_ms / max(fl_n, 1),
@@ -551,7 +615,7 @@ def main():
         out["ms_per_step_weak"] = elapsed_weak / args.steps * 1e3
     if sec:
         out.update(sec)
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         out["cpu_baseline"], out["cpu_baseline_allcores"] = cpu_baseline(
             v, f, args.cpu_queries, lambda k: np.ascontiguousarray(q_all[:k].cpu().numpy()))
     print(json.dumps(out), flush=True)

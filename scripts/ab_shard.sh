@@ -13,7 +13,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   ORDER=$VS; [ $((r % 2)) -eq 0 ] && ORDER=$RVS
   for qn in ${QS:-12500000 100000000}; do
     for v in $ORDER; do
-      MESH_AMD_LIB=$PWD/build/variants/$v.so timeout -k 10 300 python bench.py --queries $qn --steps ${VSTEPS:-10} \
+      MESH_AMD_LIB=$PWD/build/variants/$v.so timeout -k 10 300 python bench.py --full --queries $qn --steps ${VSTEPS:-10} \
         --warmup 2 --no-cpu >> gpurun_out/abs_${v}_$qn.log 2>&1
       rc=$?
       echo "abs_$v $qn round $r rc=$rc" | tee -a gpurun_out/abs_status.txt

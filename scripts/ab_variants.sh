@@ -18,7 +18,7 @@ for v in $VS; do
 done
 for r in $(seq 1 ${ROUNDS:-2}); do
   for v in $VS; do
-    MESH_AMD_LIB=$PWD/build/variants/$v.so timeout -k 10 300 python bench.py --queries ${VQ:-100000000} --steps ${VSTEPS:-10} \
+    MESH_AMD_LIB=$PWD/build/variants/$v.so timeout -k 10 300 python bench.py --full --queries ${VQ:-100000000} --steps ${VSTEPS:-10} \
       --warmup 2 --no-cpu >> gpurun_out/ab_$v.log 2>&1
     rc=$?
     echo "ab_$v round $r rc=$rc" | tee -a gpurun_out/ab_status.txt

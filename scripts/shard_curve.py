@@ -20,9 +20,10 @@ def main():
     args = ap.parse_args()
     rows = []
     for n_gpu, q in ((8, 12_500_000), (4, 25_000_000), (2, 50_000_000), (1, 100_000_000)):
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--queries", str(q), "--steps",
-                              str(args.steps), "--warmup", "2", "--no-cpu"], check=True, capture_output=True,
-                             text=True, timeout=600).stdout
+        # --full: the curve records the roofline's node and leaf counts (the instrumented traversal)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--queries", str(q),
+                              "--steps", str(args.steps), "--warmup", "2", "--no-cpu"], check=True,
+                             capture_output=True, text=True, timeout=600).stdout
         d = json.loads(out.strip().splitlines()[-1])
         rows.append({"shard_of_N": n_gpu, "queries": q, "ms_per_step": d["ms_per_step"],
                      "queries_per_s": d["value"], "ns_per_query": d["ms_per_step"] * 1e6 / q,
