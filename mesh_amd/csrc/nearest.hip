@@ -24,6 +24,7 @@
 //     Aila & Laine, dealt to every lane of the wave).  Pass 1 runs over super-leader slots, then leader
 //     slots, then followers, each starting from the leaf of its nearest leader's answer.
 //     The fp32 pruning radius is cached per lane and refreshed only when the best distance changes.
+//     The cut-started unled launch of a sorted call (the headline) runs the lean instantiation (MSH_KNN_LEAN).
 //     A lane that exceeds `budget` node steps stops and appends its query (with its exact best so far)
 //     to a deferred list: queries near the centre of a closed surface are equidistant from most of it
 //     and would otherwise hold their whole wave for ~10^6 steps.
@@ -35,6 +36,7 @@
 // Ties: the lexicographic minimum of (squared distance, face index) — deterministic and independent of
 // traversal order or of how the work was split (every box within best*(1+2^-40) is visited).
 #include <algorithm>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -411,6 +413,61 @@ struct WalkerT {
         if (PF && r && node >= 0) node_prefetch(nodes, node, wsl);
         return r;
     }
+    // step_collect<PF = true> of the lean pass-1 kernel (k_knn LEAN).  The caller keeps two ring places free, so
+    // both leaf children are always handed back and no leaf is parked by the step itself (`node < 0` still enters:
+    // cut records hold ~leaf refs).  One wave-uniform test covers the deep stack: when no lane of the step holds
+    // kStack entries or more, the push writes LDS (index sp < kStack) and every pop reads it (indices < sp <= kStack),
+    // so the common step carries no spill branch; spill_of() yields this lane's global spill column, only when needed.
+    template <class Pol, class SpillOf>
+    __device__ inline bool step_list(const BNode* __restrict__ nodes, const QF& qf, const Pol& pol, Ent* __restrict__ lds,
+                                     SpillOf&& spill_of, int& p0, int& p1, const float4* nb, uint32_t wsl) {
+        const bool deep = __ballot(sp >= kStack) != 0ull;
+        bool more = false;
+        if (node < 0) {
+            p0 = ~node;
+        } else {
+            const NodeV nd = node_from_lds(nb);
+            float d0, d1;
+            node_child_bounds(nd, qf, d0, d1);
+            const int c0 = nd.child(0), c1 = nd.child(1);
+            const float lim = pol.limf;
+            const bool h0 = d0 <= lim, h1 = d1 <= lim;
+            const bool l0 = h0 && c0 < 0, l1 = h1 && c1 < 0;
+            const bool i0 = h0 && c0 >= 0, i1 = h1 && c1 >= 0;
+            const bool first1 = d1 < d0;
+            if (l0) p0 = ~c0;
+            if (l1) p1 = ~c1;
+            if (i0 && i1) {
+                const Ent e = E::make((unsigned)(first1 ? c0 : c1), __float_as_uint(first1 ? d0 : d1));
+                if (!deep)
+                    lds[sp * kBlock] = e;
+                else
+                    stack_put(lds, spill_of(), sp, e);
+                ++sp;
+            }
+            if (i0 || i1) {
+                node = (i0 && i1) ? (first1 ? c1 : c0) : (i0 ? c0 : c1);
+                more = true;
+            }
+        }
+        if (!more) {
+            if (!deep) {
+                while (sp > 0) {
+                    --sp;
+                    const Ent e = lds[sp * kBlock];
+                    if (E::bound(e) <= pol.limf) {
+                        node = E::ref(e);
+                        more = true;
+                        break;
+                    }
+                }
+            } else {
+                more = pop(pol, lds, spill_of());
+            }
+        }
+        if (more && node >= 0) node_prefetch(nodes, node, wsl);
+        return more;
+    }
 };
 typedef WalkerT<Ent8> Walker;
 
@@ -474,6 +531,56 @@ __device__ inline void write_result(const KnnArgs& a, size_t i, const D3& q, con
         a.out_w[3 * r + 2] = w.z;
     }
 }
+
+// write_result of the lean pass-1 kernel (k_knn LEAN): the sorted path's direct stores to the caller's row r, and
+// nothing else (no slot-order record, no unsorted form).
+template <int MODE, class Pol>
+__device__ inline void write_direct(const TriRec* __restrict__ tris, size_t r, const D3& q, const Pol& pol,
+                                    uint32_t* out_face, uint32_t* out_part, double* out_pt, double* out_w) {
+    D3 ta, tb, tc, o = D3{NAN, NAN, NAN}, w = D3{NAN, NAN, NAN};
+    uint32_t face = MSH_NO_FACE;
+    int part = 0;
+    if (pol.best_leaf >= 0) {  // < 0 only for a non-finite query
+        load_tri(tris, pol.best_leaf, ta, tb, tc, face);
+        closest_on_triangle(q, ta, tb, tc, o, part);
+        if (MODE == 3) w = heidrich_bary(o, ta, tb, tc);
+    }
+    out_face[r] = face;
+    if (MODE == 0 && out_part) out_part[r] = (uint32_t)part;
+    out_pt[3 * r] = o.x;
+    out_pt[3 * r + 1] = o.y;
+    out_pt[3 * r + 2] = o.z;
+    if (MODE == 3) {
+        out_w[3 * r] = w.x;
+        out_w[3 * r + 1] = w.y;
+        out_w[3 * r + 2] = w.z;
+    }
+}
+
+// A kernel argument read from the kernarg segment at the point of use (the lean pass-1 kernel's cold fields: the
+// deferral, resume and spill-area arguments and the output pointers, used once per tile after its wave loop).  The
+// empty asm hides the segment's address from the optimiser, which otherwise loads every field of the by-value
+// KnnArgs at kernel entry and keeps it in SGPRs (or in lanes of a spill VGPR) across the loop.  KnnArgs is the
+// kernel's only argument, so a field's kernarg offset is its offsetof.
+static_assert(std::is_standard_layout<KnnArgs>::value && std::is_trivially_copyable<KnnArgs>::value &&
+                  alignof(KnnArgs) <= 8,
+              "cold_arg reads KnnArgs fields at their offsetof from the start of the kernarg segment");
+template <class T>
+__device__ inline T cold_arg(size_t off) {
+    typedef __attribute__((address_space(4))) const char* KP;
+    KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(__attribute__((address_space(4))) const T*)(p + off);
+}
+// (MSH_LEAN_COLD 0: the plain by-value field of the kernel's `a`, for the A/B)
+#ifndef MSH_LEAN_COLD
+#define MSH_LEAN_COLD 1
+#endif
+#if MSH_LEAN_COLD
+#define MSH_COLD_ARG(f) cold_arg<decltype(KnnArgs::f)>(offsetof(KnnArgs, f))
+#else
+#define MSH_COLD_ARG(f) (a.f)
+#endif
 
 template <int MODE>
 struct PolOf { using T = TriPol; };
@@ -609,6 +716,46 @@ constexpr int kPend = MSH_KPEND;
 #define MSH_TILE_PF 1
 #endif
 
+// Lean pass-1 kernel (k_knn LEAN): the headline launch -- every slot in one unled launch, started from a narrow entry
+// cut, direct stores -- gets an instantiation without the leader / follower starts, the T == 1 path, wide cut
+// records, slot-order records and the inv_w store.  80 SGPR spills (lanes of two VGPRs, read back inside the wave
+// loop) -> 3, none in the loop; 8 VGPR spills -> 2; 9,500 -> 3,100 instructions (profiles/r07_knn_lean_isa.txt).
+// C3 100M, G q/s, builds interleaved in one session each (profiles/r07_c3_knn_lean_ab.jsonl):
+//   generic kernel (parent)                          2.543 2.547 2.591 | 2.569 2.574 2.572 | 2.559 2.541 2.531 2.533 2.533
+//   lean, dead paths out only (STEP 0, COLD 0)       2.498 2.502 2.523   (38 SGPR spills; slower than the parent)
+//   + MSH_LEAN_COLD: cold arguments read where used  2.533 2.562 2.537
+//   + MSH_LEAN_STEP: step_list, two ring places kept 2.599 2.598 2.596 | 2.594 2.594 2.600 | 2.586 2.563 2.557 2.552 2.557
+//   + MSH_LEAN_STATE: walk state in one VGPR                                                | 2.588 2.589 2.588 2.587 2.591
+// and a fifth session of six runs each: parent 2.533-2.557; lean with cold arguments only 2.420-2.496; + step_list
+// 2.544-2.564; + packed state 2.592-2.610 (the state's slowest run 1.1 % over the fastest without it, whose runs spread
+// by 0.8 %; step and state together 3.8 % over the build without either, whose runs spread by 3.2 %).
+// MSH_LEAN_COLD: the deferral, resume, spill-area and output arguments are read from the kernarg segment after the
+// tile's wave loop (cold_arg) instead of living in SGPRs across it.  MSH_LEAN_STEP: the node step without the
+// park-the-farther-leaf branch (a lane walks while two ring places are free) and with the deep-stack case behind one
+// wave-uniform test (WalkerT::step_list).  MSH_LEAN_STATE: active / want_defer / deferred as one per-lane register
+// instead of three lane masks kept by ~25 scalar instructions per iteration.  Each 0 restores the generic form inside
+// the lean kernel, for the A/B; MSH_KNN_LEAN 0: every launch runs the generic kernel.
+// Rejected (same sessions): a 4-B load of each appended leaf's record into a register nothing reads, so that its round
+// finds it in cache -- 2.496 when the next step's vmcnt(0) waits for it, 2.505-2.510 (one load per iteration) and
+// 2.465-2.470 (two) when the step's wait leaves them in flight: the rounds' loads are not what the wave waits for, and
+// the extra vector-memory instructions cost 3-5 %.  Loading the next round's triangle before the current round's
+// fp64 work needs 20 more VGPRs than the 2 the kernel has left.
+#ifndef MSH_KNN_LEAN
+#define MSH_KNN_LEAN 1
+#endif
+// MSH_LIST_RESERVE 1 (a counting build, not shipped): the generic list kernel keeps the two ring places free too, so
+// its step never parks a leaf and it visits what the lean kernel visits; instrumented launches (msh_tree_nearest_stats)
+// run the generic kernel, and this is how the reserve's effect on the node and leaf counts is measured.
+#ifndef MSH_LIST_RESERVE
+#define MSH_LIST_RESERVE 0
+#endif
+#ifndef MSH_LEAN_STEP
+#define MSH_LEAN_STEP 1
+#endif
+#ifndef MSH_LEAN_STATE
+#define MSH_LEAN_STATE 1
+#endif
+
 constexpr unsigned kRing = 256;     // ring entries per wave: < 64 left after full rounds + <= 128 per step
 constexpr size_t kListMaxLeaves = (size_t)1 << 26;  // leaf index bits of a ring entry
 constexpr size_t kLeadMinLeaves = 4096;  // smaller trees skip the leader phases (C1: 0.56 -> 0.29 ms)
@@ -672,16 +819,45 @@ __device__ inline bool cut_start(const KnnArgs& a, size_t cell, const Pol& pol, 
     }
     return w.pop(pol, lds, spill);
 }
+// cut_start of the lean pass-1 kernel: 32-B records only, and the walk starts with an empty stack, so the kCutK
+// entries and the pop that follows stay in LDS
+static_assert(kCutK <= kStack, "a cut record's entries fit the LDS stack");
+template <class Pol, class W>
+__device__ inline bool cut_start_narrow(const uint32_t* __restrict__ cut, size_t cell, const Pol& pol, W& w,
+                                        uint32_t* __restrict__ lds) {
+    const uint4* c = reinterpret_cast<const uint4*>(cut + cell * 8);
+    const uint4 e0 = c[0], e1 = c[1];
+    const uint32_t e[kCutK] = {e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
+#pragma unroll
+    for (int j = kCutK - 1; j >= 0; --j)
+        if ((int)e[j] >= 0) {
+            lds[w.sp * kBlock] = Ent4::make((uint32_t)Ent4::ref(e[j]), e[j] & 0xFFE00000u);
+            ++w.sp;
+        }
+    while (w.sp > 0) {
+        --w.sp;
+        const uint32_t t = lds[w.sp * kBlock];
+        if (Ent4::bound(t) <= pol.limf) {
+            w.node = Ent4::ref(t);
+            return true;
+        }
+    }
+    return false;
+}
 
 // PF (list path, trees of <= 2^20 leaves): 4-B stack entries (Ent4) and each lane's next node prefetched into LDS
 // (node_prefetch); the 16 KB the node slots take per block come out of the stack.  C3: 1889 -> 1945 M q/s in one
 // session, wave-cycles waiting on memory 55.7 -> 46.7 % at +10 VALU instructions per query
 // (profiles/r04_c3_node_prefetch_lds_ab.jsonl).
-template <int MODE, bool STATS, bool LIST, bool PF>
+template <int MODE, bool STATS, bool LIST, bool PF, bool LEAN = false>
 __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
     constexpr bool kCompact = MODE == 0 || MODE == 3;  // per-lane queues dealt to the wave (else: per-lane rounds)
     constexpr bool kList = (MODE == 0 || MODE == 3) && LIST;  // a separate instantiation: its own registers
     constexpr bool kPF = kList && PF;  // 4-B stack entries and nodes prefetched into LDS
+    constexpr bool kLean = LEAN;       // the cut-started unled launch only (launch_knn's pass1; MSH_KNN_LEAN)
+    constexpr bool kLeanStep = LEAN && MSH_LEAN_STEP;  // with the straighter node step (step_list)
+    constexpr bool kLeanState = LEAN && MSH_LEAN_STATE;  // with the lane's walk state packed in one register
+    static_assert(!LEAN || (kPF && !STATS), "the lean kernel is a list-path, prefetching, uninstrumented one");
     typedef typename std::conditional<kPF, Ent4, Ent8>::type E;
     __shared__ typename E::T stk[kStack * kBlock];
     __shared__ float4 nbuf[kPF ? 4 * kBlock : 1];
@@ -697,7 +873,8 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
     const uint32_t wsl = (uint32_t)(size_t)(__attribute__((address_space(3))) float4*)(nbuf + (kPF ? wv_u * 256 : 0));
     const float4* nb = nbuf + (kPF ? (tid >> 6) * 256 + lane : 0);
     uint2* ent = lent + (kCompact ? (tid >> 6) * 64 * kLeafQ : 0);
-    uint2* spill = a.spill ? a.spill + (size_t)blockIdx.x * kBlock * (size_t)a.spill_depth + tid : nullptr;
+    // (lean: the spill column is worked out where a deep stack needs it, lean_spill below)
+    uint2* spill = (!kLeanStep && a.spill) ? a.spill + (size_t)blockIdx.x * kBlock * (size_t)a.spill_depth + tid : nullptr;
     const unsigned group = blockIdx.x & 7u;
     unsigned long long u_trav_it = 0, u_trav_lanes = 0, u_leaf_it = 0, u_leaf_lanes = 0;  // STATS: wave iterations
     unsigned n_nodes = 0, n_leaves = 0;
@@ -722,24 +899,40 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
         // a lane without a query (past the phase's units, or a non-finite row) only helps
         const size_t k = (size_t)tile * 64 + lane;
         size_t i = 0;
-        bool live = k < a.nunits;
+        bool live = k < (kLean ? a.S : a.nunits);  // lean: phase 0, every slot
         if (live) {
-            i = slot_of(a, k);
+            i = kLean ? k : slot_of(a, k);
             live = i < a.S;
         }
         const D3 q = live ? load_q(a, i) : D3{0.0, 0.0, 0.0};
 #if MSH_TILE_PF
         if (lane == 0) nxt = glo < ghi ? atomicAdd(&a.counters[group * 32], 1u) : ~0u;
 #endif
-        if (live && a.inv_w && !a.direct) a.inv_w[a.qperm[i]] = (uint32_t)i;
+        if constexpr (!kLean)
+            if (live && a.inv_w && !a.direct) a.inv_w[a.qperm[i]] = (uint32_t)i;
         auto pol = make_pol<MODE>(a, i, q);
         const bool fin = live && finite3(q);
+        // lean: the sorted path's direct stores to the caller's row, their arguments fetched here (cold_arg)
+        auto lean_write = [&]() {
+            if constexpr (kLean)
+                write_direct<MODE>(static_cast<const TriRec*>(a.leaves), (size_t)MSH_COLD_ARG(perm)[i], q, pol,
+                                   MSH_COLD_ARG(out_face), MSH_COLD_ARG(out_part), MSH_COLD_ARG(out_pt),
+                                   MSH_COLD_ARG(out_w));
+        };
         if (live && !fin) {  // no distance is defined: NO_FACE / NaN, no traversal
-            if (!STATS || a.res) write_result<MODE>(a, i, q, pol);
+            if constexpr (kLean)
+                lean_write();
+            else if (!STATS || a.res)
+                write_result<MODE>(a, i, q, pol);
         }
         int hint_leaf = -1;  // STATS
         const size_t cell = kList && fin ? cut_cell(a, q) : kNoCell;
-        if constexpr (MODE == 0 || MODE == 3) {
+        if constexpr (kLean) {
+            if (cell != kNoCell) {  // the cell's hint leaf, as below
+                const int lf = (int)a.cut[cell * 8];
+                if (lf >= 0) pol.test(lf);
+            }
+        } else if constexpr (MODE == 0 || MODE == 3) {
             if (kList && a.cut && cell != kNoCell && a.phase != 2) {
                 // slots without a leader (super-leaders, leaders, unled launches) inside the grid: the cell's hint
                 // leaf (the closest face found for its centre), within U(c) + r of q's own answer
@@ -778,7 +971,7 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
 #endif
             }
         }
-        if (a.T == 1) {
+        if (!kLean && a.T == 1) {
             if (fin) {
                 pol.test(0);
                 if (STATS) ++n_leaves;
@@ -789,20 +982,42 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
         if constexpr (kList) {
           {
             QF qf;
-            const int root = query_root(a, i, q, qf);
+            int root = 0;
+            if constexpr (kLean) {  // single tree
+                const double o[3] = {a.org[0], a.org[1], a.org[2]};
+                qf = make_qf(q, o, a.tm);
+            } else {
+                root = query_root(a, i, q, qf);
+            }
             WalkerT<E> w{root, 0};
             bool start = fin;
-            if (cell != kNoCell) start = cut_start(a, cell, pol, w, lds, spill);
+            if constexpr (kLeanStep) {
+                if (cell != kNoCell) start = cut_start_narrow(a.cut, cell, pol, w, lds);
+            } else {
+                if (cell != kNoCell) start = cut_start(a, cell, pol, w, lds, spill);
+            }
+            auto lean_spill = [&]() -> uint2* {
+                return MSH_COLD_ARG(spill) + (size_t)blockIdx.x * kBlock * (size_t)MSH_COLD_ARG(spill_depth) + tid;
+            };
             if (kPF && start && w.node >= 0) node_prefetch(a.nodes, w.node, wsl);
             uint32_t* ring = lsh + (tid >> 6) * (kRing + 64 * 4);
             unsigned long long* bd = reinterpret_cast<unsigned long long*>(ring + kRing);  // per owner: d2 bits
             unsigned long long* bfl = bd + 64;                                              // (face << 32 | leaf)
             bool active = start, want_defer = false, deferred = false;
+            // lean (kLeanState): the three flags as one VGPR -- 0 idle, 1 walking, 2 past its budget (its own leaves
+            // still wait), 3 deferred -- instead of three lane masks the compiler updates with scalar code at every
+            // iteration
+            enum { kIdle = 0, kWalk = 1, kPast = 2, kDeferred = 3 };
+            int st = start ? kWalk : kIdle;
             int nq = 0;              // this lane's leaves appended since all of them were last evaluated (a bound)
             unsigned last_pos = 0;   // ring counter of this lane's newest entry
             unsigned head = 0, tail = 0;  // wave-uniform ring counters: entries [head, tail) wait
             unsigned steps = 0;
             const unsigned max_steps = (unsigned)min(a.T, (size_t)UINT_MAX);
+            unsigned budget = a.budget;
+            // lean: held in an SGPR (left alone, the compiler reloads it from the kernarg segment at every step and
+            // waits for it)
+            if constexpr (kLean) asm volatile("" : "+s"(budget));
             unsigned tot = 0;  // STATS: node steps of this lane, restarts included
             // Evaluate ring entries [head, upto) in rounds of 64, one per lane: each lane tests its entry's leaf
             // against its owner's query (ds_bpermute); the owners publish their best before each round and take
@@ -847,20 +1062,30 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
                 }
                 if ((int)(last_pos - head) < 0) nq = 0;  // every entry of this lane is evaluated
             };
-            unsigned dslot = 0;  // this lane's deferred-list slot (deferred)
+            unsigned dslot = ~0u;  // this lane's deferred-list slot (deferred)
+          lean_again:
             for (;;) {
                 // a lane past its budget defers once its own leaves are evaluated (pass 2 then owns the query); its
                 // records are written after the tile's loop, so the loop holds no copy of the construction
-                if (want_defer && nq == 0) {
+                if constexpr (kLeanState) {
+                    if (st == kPast && nq == 0) st = kDeferred;
+                } else if (want_defer && nq == 0) {
                     want_defer = false;
-                    dslot = atomicAdd(a.n_deferred, 1u);
-                    if (dslot < a.max_deferred) {
+                    if constexpr (kLean) {  // its slot is claimed after the loop, with the list's arguments
                         active = false;
                         deferred = true;
+                    } else {
+                        dslot = atomicAdd(a.n_deferred, 1u);
+                        if (dslot < a.max_deferred) {
+                            active = false;
+                            deferred = true;
+                        }
+                        // deferred list full: finish here without a budget
                     }
-                    // deferred list full: finish here without a budget
                 }
-                const bool can = active && !want_defer && nq < kPend;
+                // lean: two ring places stay free, so a step hands back both leaf children (step_list)
+                const bool can = (kLeanState ? st == kWalk : active && !want_defer) &&
+                                 nq < ((kLeanStep || MSH_LIST_RESERVE) ? kPend - 1 : kPend);
                 const bool any = __ballot(can) != 0ull;
                 if (!any && tail == head) break;  // nothing queued and nobody can move: the tile is done
                 if (STATS) {
@@ -872,12 +1097,19 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
                 }
                 int l0 = -1, l1 = -1;
                 if (can) {
-                    active = w.template step_collect<decltype(pol), STATS, kPF>(a.nodes, qf, pol, lds, spill, n_nodes,
-                                                                                  l0, l1, kPend - nq, nb, wsl);
+                    if constexpr (kLeanStep)
+                        active = w.step_list(a.nodes, qf, pol, lds, lean_spill, l0, l1, nb, wsl);
+                    else
+                        active = w.template step_collect<decltype(pol), STATS, kPF>(a.nodes, qf, pol, lds, spill,
+                                                                                      n_nodes, l0, l1, kPend - nq, nb,
+                                                                                      wsl);
                     ++steps;
                     if (STATS) ++tot;
                     if (active && steps >= max_steps) active = false;  // each node is entered once: corrupt tree
-                    if (active && steps == a.budget) want_defer = true;
+                    if constexpr (kLeanState)  // (the flags stay out of it: `active` is this step's result only)
+                        st = !active ? kIdle : (steps == budget ? kPast : kWalk);
+                    else if (active && steps == budget)
+                        want_defer = true;
                 }
                 // append this step's leaves (at most two per lane) to the ring, in lane order
                 if (l0 < 0) {
@@ -901,7 +1133,57 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
                 const unsigned upto = any ? head + ((tail - head) & ~63u) : tail;
                 if (upto != head) run_rounds(upto);
             }
-            if (deferred) {
+            if constexpr (kLean) {
+                // claim the deferred lanes' list slots; with the list full a lane takes its walk up again where it
+                // stopped (its pending node is still prefetched), now without a budget: steps is past it
+                bool again = false;
+                const unsigned max_deferred = MSH_COLD_ARG(max_deferred);
+                if constexpr (kLeanState) deferred = st == kDeferred;
+                if (deferred && dslot == ~0u) {
+                    dslot = atomicAdd(MSH_COLD_ARG(n_deferred), 1u);
+                    if (dslot >= max_deferred) {
+                        deferred = false;
+                        active = true;
+                        st = kWalk;
+                        again = true;
+                    }
+                }
+                if (__ballot(again) != 0ull) goto lean_again;
+                // only a lane that holds a slot of the list is deferred: steps is past the budget after a refused
+                // claim, so neither form of the walk state asks to defer a second time
+                deferred = deferred && dslot < max_deferred;
+            }
+            if constexpr (kLean) {
+              if (deferred) {
+                DeferRec r;
+                r.slot = (uint32_t)i;
+                r.face = pol.best_face;
+                r.leaf = pol.best_leaf;
+                r.roff = 0;
+                r.best = pol.best;
+                r.rcnt = 0;
+                r.sbound = 0x7F800000u;  // +inf
+                unsigned long long* const max_best = MSH_COLD_ARG(max_best);
+                if (max_best) atomicMax(max_best, (unsigned long long)__double_as_longlong(pol.best));
+                uint2* const resume = MSH_COLD_ARG(resume);
+                if (resume) {
+                    const unsigned cnt = (unsigned)w.sp + 1;
+                    const unsigned off = atomicAdd(MSH_COLD_ARG(n_resume), cnt);
+                    if (off + cnt <= MSH_COLD_ARG(resume_cap)) {
+                        uint2* dst = resume + off;
+                        const uint2* sp_col = w.sp > kStack ? lean_spill() : nullptr;
+                        for (int j = 0; j < w.sp; ++j) {
+                            const typename E::T e = stack_get(lds, sp_col, j);
+                            dst[j] = make_uint2((uint32_t)E::ref(e), __float_as_uint(E::bound(e)));
+                        }
+                        dst[w.sp] = make_uint2((uint32_t)w.node, 0u);
+                        r.roff = off;
+                        r.rcnt = cnt;
+                    }
+                }
+                MSH_COLD_ARG(deferred)[dslot] = r;
+              }
+            } else if (deferred) {
                 if ((a.phase == 1 || a.phase == 3 || a.phase == 4) && a.res) {
                     // later phases take hints from this slot before pass 2 answers it: publish the closest point of
                     // the best face so far (a point on the mesh), or NO_FACE when it has none yet
@@ -962,7 +1244,11 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
             }
             if (STATS && fin && hint_leaf >= 0 && pol.best_leaf == hint_leaf) ++n_hint_won;
             if (deferred) continue;
-            if (fin && (!STATS || a.res)) write_result<MODE>(a, i, q, pol);
+            if constexpr (kLean) {
+                if (fin) lean_write();
+            } else {
+                if (fin && (!STATS || a.res)) write_result<MODE>(a, i, q, pol);
+            }
             continue;
           }
         }
@@ -1555,6 +1841,10 @@ static int launch_knn(msh_tree* tree, KnnArgs a, hipStream_t s, const char* time
     const bool lead = kLead > 1 && (MODE == 0 || MODE == 3) && a.res != nullptr && a.S >= 64 * (size_t)kLead &&
                       a.T >= kLeadMinLeaves && !(a.list && a.cut);
     a.max_deferred = (unsigned)std::min<size_t>(a.S, (a.S / 16) + 65536);
+    // test hook: a shorter deferred list, so that a few rows past their budget fill it (a lane that finds it full
+    // finishes its walk in pass 1 without a budget)
+    if (const char* e = getenv("MESH_AMD_MAX_DEFERRED"))
+        a.max_deferred = std::min<unsigned>(a.max_deferred, (unsigned)std::max(1, atoi(e)));
     DevBuf& dbuf = ws.flags;
     MSH_TRY(dbuf.reserve((size_t)a.max_deferred * sizeof(DeferRec)));
     a.deferred = dbuf.as<DeferRec>();
@@ -1578,6 +1868,13 @@ static int launch_knn(msh_tree* tree, KnnArgs a, hipStream_t s, const char* time
         a.resume_cap = (unsigned)cap;
     }
 #endif
+    // the lean kernel takes the cut-started unled launch (k_knn LEAN); test hook MESH_AMD_KNN_LEAN=0: the generic one
+    bool lean = false;
+    if constexpr (MSH_KNN_LEAN && !STATS && (MODE == 0 || MODE == 3)) {
+        const char* e = getenv("MESH_AMD_KNN_LEAN");
+        lean = (!e || atoi(e) != 0) && a.list && list_pf && a.cut && !a.cut_wide && a.direct && a.T > 1 &&
+               !a.orgs;
+    }
     auto pass1 = [&](int phase, size_t nunits, const char* name) -> int {
         a.phase = phase;
         a.budget = phase == 3 ? kBudget3 : ((phase == 1 || phase == 4) ? kBudget1 : kBudget);
@@ -1589,8 +1886,12 @@ static int launch_knn(msh_tree* tree, KnnArgs a, hipStream_t s, const char* time
         a.ntiles = (unsigned)((nunits + 63) / 64);
         const unsigned nblk = std::min<unsigned>((a.ntiles + 3) / 4, ncu * kKnnBlocksPerCU);
         if (nblk == 0) return MSH_OK;
-        TimedLaunch t1(name, s);
-        if (a.list)
+        const bool take_lean = lean && phase == 0;
+        TimedLaunch t1(take_lean ? "knn_lean" : name, s);  // its own timer name: tests tell the two kernels apart
+        constexpr bool kCanLean = MSH_KNN_LEAN && !STATS && (MODE == 0 || MODE == 3);
+        if (take_lean) {
+            if constexpr (kCanLean) k_knn<MODE, false, true, true, true><<<nblk, kBlock, 0, s>>>(a);
+        } else if (a.list)
             if (list_pf)
                 k_knn<MODE, STATS, (MODE == 0 || MODE == 3), (MODE == 0 || MODE == 3)><<<nblk, kBlock, 0, s>>>(a);
             else

@@ -45,11 +45,28 @@ def pmc_of(target, kernel, units):
                     "(2 FETCH_SIZE + WRITE_SIZE) KB per dispatch, gfx950 correction"}
 
 
+# pass 1 of the closest-point traversal: the lean kernel of cut-started sorted launches, the generic one, and the
+# generic one's name in profiles taken before the lean kernel existed
+PASS1_KERNELS = ("msh::k_knn<0, false, true, true, true>", "msh::k_knn<0, false, true, true, false>",
+                 "msh::k_knn<0, false, true, true>")
+
+
+def pass1_kernel(target):
+    """the pass-1 kernel that the config's PMC profile holds (the first of PASS1_KERNELS in it)"""
+    try:
+        with open(os.path.join(ROOT, "profiles", "pmc_configs.json")) as fh:
+            ks = json.load(fh).get(target, {}).get("kernels", {})
+    except (OSError, ValueError):
+        ks = {}
+    return next((k for k in PASS1_KERNELS if k in ks), PASS1_KERNELS[0])
+
+
 def pmc_traversal(target, S):
     """Measured fabric bytes per query of the closest-point traversal (pass-1 launches + pass 2) in a config's
     PMC profile: every dispatch's bytes over (traversals x S), the profile's traversals = pass-2 dispatches (the
     entry cut's traversal dropped by pmc_configs.py --skip 1)."""
-    k1, k2 = "msh::k_knn<0, false, true, true>", "msh::k_knn_coop<0, false>"
+    k2 = "msh::k_knn_coop<0, false>"
+    k1 = pass1_kernel(target)
     a, b = pmc_of(target, k1, 1), pmc_of(target, k2, 1)
     if "hbm_bytes_per_unit" not in a or "hbm_bytes_per_unit" not in b:
         return a if "hbm_bytes_per_unit" not in a else b

@@ -2,10 +2,12 @@
 """Register-pressure check of the closest-point traversal kernel (CPU only, no GPU needed).
 
 Compiles mesh_amd/csrc/nearest.hip to gfx950 assembly (optionally with extra -D flags) and reports, for
-k_knn<MODE, false, LIST, PF>, the VGPR count, the spill count and how many scratch (spill) instructions sit inside
-the tile's traversal loop (LLVM's block annotations "in Loop: ... Depth=N", N >= 2).  A spill reload
-inside that loop costs a memory round trip per iteration: A/B runs showed -13 % for two such reloads, so a
-variant with loop spills is not worth a GPU session.
+k_knn<MODE, false, LIST, PF, LEAN>, the register and spill counts of the code object's metadata, and what sits inside
+the tile's wave loop (found from LLVM's loop annotations as the parent of the loop with the fp64 construction): scratch (VGPR spill) instructions,
+lane reads and writes (v_readlane / v_writelane: SGPR spill traffic), and the static VALU / SALU / branch counts, split
+into the leaf rounds (the innermost loop that holds the fp64 construction) and the node step (the rest of the wave
+loop).  A spill reload inside that loop costs a memory round trip per iteration: A/B runs showed -13 % for two such
+reloads, so a variant with loop spills is not worth a GPU session.
 
     python scripts/isa_check.py [-DMSH_LEAF_Q=4 ...]
 """
@@ -30,38 +32,117 @@ def compile_asm(flags):
     return s
 
 
-def report(s, mode):
-    name = f"_ZN3msh5k_knnILi{mode}ELb0ELb{int(LIST)}ELb{int(PF)}EEEvNS_7KnnArgsE"
+def blocks(body):
+    """(label, loops, lines) per basic block of a kernel's assembly; loops = headers of the loops that hold the
+    block, outermost first (LLVM's "Parent Loop" / "This Loop Header" / "in Loop: Header=" annotations)."""
+    out, cur, loops, label = [], [], [], "entry"
+    chain = {}  # loop header -> its chain of headers
+    lines = body.split("\n")
+    for k, line in enumerate(lines):  # headers first: a block can precede its loop's header in the layout
+        if line.startswith(".LBB"):
+            note = [line]
+            while k + 1 < len(lines) and lines[k + 1].lstrip().startswith(";") and "Loop" in lines[k + 1]:
+                k += 1
+                note.append(lines[k])
+            note = "\n".join(note)
+            if "Loop Header: Depth=" in note:
+                lab = line.split(":")[0].lstrip(".L")
+                chain[lab] = re.findall(r"Parent Loop (\w+) Depth=", note) + [lab]
+    k = 0
+    while k < len(lines):
+        line = lines[k]
+        if line.startswith(".LBB") or line.startswith("; %bb"):
+            if cur:
+                out.append((label, loops, cur))
+            label, cur = line.split(":")[0].lstrip(".L"), []
+            note = [line]
+            while k + 1 < len(lines) and lines[k + 1].lstrip().startswith(";") and "Loop" in lines[k + 1]:
+                k += 1
+                note.append(lines[k])
+            note = "\n".join(note)
+            m = re.search(r"in Loop: Header=(\w+) Depth=", note)
+            if m:
+                loops = chain.get(m.group(1), [m.group(1)])
+            elif "Loop Header: Depth=" in note:
+                loops = re.findall(r"Parent Loop (\w+) Depth=", note) + [label]
+                chain[label] = loops
+            else:
+                loops = []
+            k += 1
+            continue
+        t = line.strip()
+        if t and not t.startswith(";") and not t.startswith("."):
+            cur.append(t)
+        k += 1
+    if cur:
+        out.append((label, loops, cur))
+    return out
+
+
+def classify(ins):
+    op = ins.split()[0]
+    if op.startswith("s_cbranch") or op == "s_branch":
+        return "branch"
+    if op.startswith("v_"):
+        return "valu"
+    if op.startswith("s_"):
+        return "salu"
+    return "mem"
+
+
+def report(s, mode, lst, pf, lean):
+    name = f"_ZN3msh5k_knnILi{mode}ELb0ELb{int(lst)}ELb{int(pf)}ELb{int(lean)}EEEvNS_7KnnArgsE"
     meta = s[re.search(r"\.name:\s+" + name + r"\n", s).start():][:1500]
-    vgpr = int(re.search(r"\.vgpr_count:\s+(\d+)", meta).group(1))
-    spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", meta).group(1))
+    # the metadata lists a kernel's keys in alphabetical order around .name
+    head = s[:re.search(r"\.name:\s+" + name + r"\n", s).start()][-600:]
+
+    def md(key, text):
+        m = re.findall(r"\." + key + r":\s+(\d+)", text)
+        return int(m[-1] if text is head else m[0]) if m else None
+
+    r = dict(mode=mode, list=lst, prefetch=pf, lean=lean)
+    for key in ("vgpr_count", "vgpr_spill_count", "sgpr_count", "sgpr_spill_count", "private_segment_fixed_size"):
+        r[key] = md(key, meta)
+    r["group_segment_fixed_size"] = md("group_segment_fixed_size", head)
+    # the names bench.py reads from profiles/pmc_traffic.json's isa record (waves_per_simd)
+    r["vgpr"], r["vgpr_spill"], r["lds"] = r["vgpr_count"], r["vgpr_spill_count"], r["group_segment_fixed_size"]
     a = s.index(name + ":")
     b = s.index(".end_amdhsa_kernel", a)
-    depth = 0
-    total = in_loop = 0
-    for line in s[a:b].split("\n"):
-        m = re.search(r"Depth=(\d+)", line)
-        if line.startswith(".LBB") or line.startswith("; %bb"):
-            depth = int(m.group(1)) if m else 0
-        if "scratch_" in line:
-            total += 1
-            if depth >= 2:
-                in_loop += 1
-    lds = int(re.search(r"amdhsa_group_segment_fixed_size (\d+)", s[a:b + 400]).group(1))
-    return dict(mode=mode, vgpr=vgpr, vgpr_spill=spill, scratch_ops=total, scratch_in_loop=in_loop, lds=lds)
-
-
-LIST = True  # the wave-leaf-list instantiation k_knn<MODE, false, true, PF> (the closest-point path)
-PF = True    # with LDS node prefetch and 4-B stack entries (trees of <= 2^20 leaves)
+    bl = blocks(s[a:b])
+    f64 = {}  # fp64 arithmetic per innermost loop: the leaf rounds hold the exact construction
+    for _, lp, ls in bl:
+        if len(lp) >= 2:
+            f64[lp[-1]] = f64.get(lp[-1], 0) + sum(1 for i in ls if re.match(r"v_(fma|mul|add)_f64", i))
+    leaf = max(f64, key=f64.get)
+    wave = next(lp for _, lp, _ in bl if lp and lp[-1] == leaf)[-2]  # the wave loop: the leaf rounds' parent
+    inwave = [(lp, ls) for _, lp, ls in bl if wave in lp]
+    r["scratch_ops"] = sum(1 for _, _, ls in bl for i in ls if "scratch_" in i)
+    r["scratch_in_loop"] = sum(1 for _, ls in inwave for i in ls if "scratch_" in i)
+    r["lane_rw_in_loop"] = sum(1 for _, ls in inwave for i in ls
+                               if i.startswith("v_readlane") or i.startswith("v_writelane"))
+    r["asm_lines"] = sum(len(ls) for _, _, ls in bl)
+    parts = {"leaf_round": {}, "node_step": {}}
+    for lp, ls in inwave:
+        c = parts["leaf_round" if leaf in lp else "node_step"]
+        for i in ls:
+            k = classify(i)
+            c[k] = c.get(k, 0) + 1
+            if i.startswith("s_cbranch_execz"):
+                c["execz"] = c.get("execz", 0) + 1
+            if i.startswith("s_waitcnt"):
+                c["waitcnt"] = c.get("waitcnt", 0) + 1
+            if i.startswith("s_nop"):
+                c["nop"] = c.get("nop", 0) + 1
+    r.update(parts)
+    return r
 
 
 def main():
-    global LIST, PF
     flags = sys.argv[1:]
     s = compile_asm(flags)
-    for LIST, PF in ((True, True), (True, False), (False, False)):
+    for lst, pf, lean in ((True, True, True), (True, True, False), (True, False, False), (False, False, False)):
         for mode in (0, 3):
-            print(dict(report(s, mode), list=LIST, prefetch=PF))
+            print(report(s, mode, lst, pf, lean))
 
 
 if __name__ == "__main__":

@@ -3,7 +3,7 @@
 Reads gpurun_out/pmc/<pass>/**/*counter_collection.csv (one --pmc pass per counter group) and
 *kernel_stats.csv (the --stats pass), and writes:
   profiles/pmc_traffic.json  — what bench.py reads for roofline.traffic: HBM bytes per launch of the
-                               closest-point traversal (k_knn<0,false> pass 1 + k_knn_coop<0,false> pass 2),
+                               closest-point traversal (the lean k_knn<0,false,true,true,true> pass 1 + k_knn_coop<0,false> pass 2),
                                corrected as MI355X_MICROARCH.md §HBM prescribes (gfx950 FETCH_SIZE counts a
                                coalesced 128-B request as 64 B: bytes = 2 * FETCH_SIZE + WRITE_SIZE, KB units),
                                L2 hit rate, and per-kernel counter means;
@@ -23,7 +23,7 @@ import re
 from collections import defaultdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TRAVERSAL = ("msh::k_knn<0, false, true, true>", "msh::k_knn_coop<0, false>")
+TRAVERSAL = ("msh::k_knn<0, false, true, true, true>", "msh::k_knn_coop<0, false>")
 
 
 def sys_path_root():
@@ -103,8 +103,7 @@ def isa_of_build(build_id):
     if _native.source_build_id() != build_id:
         return {"note": "sources differ from the profiled build %s: ISA not recorded" % build_id}
     try:
-        isa_check.LIST = True
-        return dict(isa_check.report(isa_check.compile_asm([]), 0), kernel=TRAVERSAL[0])
+        return dict(isa_check.report(isa_check.compile_asm([]), 0, True, True, True), kernel=TRAVERSAL[0])
     except Exception as e:  # hipcc missing: leave the field empty rather than fail the summary
         return {"note": "ISA check failed: %s" % e}
 

@@ -7,7 +7,8 @@ import csv
 import sqlite3
 import sys
 
-TRAVERSAL = ("k_knn<0, false, true, true>", "k_knn_coop<0, false>")
+# pass 1: the lean kernel of cut-started sorted launches and the generic one; pass 2
+TRAVERSAL = ("k_knn<0, false, true, true, true>", "k_knn<0, false, true, true, false>", "k_knn_coop<0, false>")
 
 con = sqlite3.connect(sys.argv[1])
 with open(sys.argv[2], "w", newline="") as fh:
@@ -16,7 +17,7 @@ with open(sys.argv[2], "w", newline="") as fh:
     for row in con.execute("select name, total_calls, total_duration, average, percentage from top_kernels"):
         w.writerow(row)
     rows = con.execute("select name, dispatch_id, duration from kernels order by dispatch_id").fetchall()
-    coop = [d for n, d, _ in rows if TRAVERSAL[1] in n]
+    coop = [d for n, d, _ in rows if TRAVERSAL[-1] in n]
     if coop:
         first = coop[0]
         for k in TRAVERSAL:
