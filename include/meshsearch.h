@@ -183,6 +183,9 @@ int msh_tree_set_entry_cut(msh_tree* tree, int G);
  * G: cells per axis of the built cut (0 if none); bytes: device bytes it holds; build_ms: GPU time of its
  * build (cell-centre queries + cut + hints).  Any output pointer may be NULL. */
 int msh_tree_entry_cut_info(const msh_tree* tree, int* state, int* G, uint64_t* bytes, double* build_ms);
+/* cells of the built cut whose start list was shortened by the build's directional rule (0 if none is built).
+ * Closest-point queries use such cells like any other; aabbtree_nearest_alongnormal starts their rays at the root. */
+int msh_tree_entry_cut_flagged(const msh_tree* tree, uint64_t* cells);
 
 /* aabbtree_nearest_alongnormal(tree, p, n) -> (dist (S,) f64, face (S,) u32, point (S,3) f64):
  * spatialsearchmodule.cpp:222-323.  Nearest hit of the rays (p, n) and (p, -n); hit point = CGAL's

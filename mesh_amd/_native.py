@@ -50,6 +50,7 @@ SIGNATURES = [
     ("msh_tree_set_entry_cut", _i, [_vp, _i]),
     ("msh_tree_query_order", _i, [_vp, _vp, _sz, _vp, _vp]),
     ("msh_tree_entry_cut_info", _i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), _c_u64_p, ctypes.POINTER(ctypes.c_double)]),
+    ("msh_tree_entry_cut_flagged", _i, [_vp, _c_u64_p]),
     ("msh_tree_nearest_alongnormal", _i, [_vp, _c_double_p, _c_double_p, _sz, _c_double_p, _c_u32_p, _c_double_p]),
     ("msh_tree_nearest_alongnormal_device", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("msh_tree_nearest_alongnormal_stats", _i, [_vp, _vp, _vp, _sz, _c_u64_p, _c_u64_p]),
@@ -245,12 +246,16 @@ class Handle(object):
     CUT_STATES = {0: "pending", 1: "built", 2: "off", 3: "failed"}
 
     def entry_cut_info(self):
-        """msh_tree_entry_cut_info -> dict(state, G, bytes, build_ms)"""
-        st, g, nb, ms = _i(0), _i(0), ctypes.c_uint64(0), ctypes.c_double(0)
+        """msh_tree_entry_cut_info -> dict(state, G, bytes, build_ms, flagged); flagged: cells whose start list the
+        build's directional rule shortened (msh_tree_entry_cut_flagged: alongnormal rays there start at the root)"""
+        st, g, nb, ms, fl = _i(0), _i(0), ctypes.c_uint64(0), ctypes.c_double(0), ctypes.c_uint64(0)
         check(lib().msh_tree_entry_cut_info(self.ptr, ctypes.byref(st), ctypes.byref(g), ctypes.byref(nb),
                                             ctypes.byref(ms)))
+        flagged = getattr(lib(), "msh_tree_entry_cut_flagged", None)  # absent from an older MESH_AMD_LIB variant
+        if flagged is not None:
+            check(flagged(self.ptr, ctypes.byref(fl)))
         return {"state": self.CUT_STATES.get(st.value, st.value), "G": g.value, "bytes": nb.value,
-                "build_ms": ms.value}
+                "build_ms": ms.value, "flagged": fl.value}
 
     def free(self):
         if self.ptr:

@@ -586,6 +586,11 @@ static int build_entry_cut(msh_tree* t, bool fine) {
     }
     const bool e4 = t->T <= kEnt4MaxLeaves;
     const size_t rb = cut_rec_bytes(t);
+    // the directional drop triples the cut launch (fp64 work per kept child: C3 coarse 3.7 -> 11.2 ms, fine 22 -> 81 ms),
+    // which a kept tree's batches repay (C3 G = 400: 42.4 -> 34.0 node visits per query) and a one-shot caller's single
+    // batch on the automatic coarse grid does not (G = 200: 47.0 -> 41.6 visits, ~2 ms of 100M rows for +8 ms of build):
+    // the fine grid and a grid the caller asked for take it, the automatic coarse grid keeps the ball rule alone
+    const bool directional = fine || t->cut_req > 0;
     hipStream_t s = t->stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     MSH_HIP(hipEventCreate(&e0));
@@ -596,10 +601,17 @@ static int build_entry_cut(msh_tree* t, bool fine) {
     }
     (void)hipEventRecord(e0, s);
     uint32_t* cut = nullptr;
+    uint64_t flagged = 0;
     int st = MSH_OK;
     {
-        DevBuf dq, df, dp, dinv, dhint;
+        DevBuf dq, df, dp, dinv, dhint, dflag;
         do {
+            if ((st = dflag.reserve(sizeof(unsigned long long))) != MSH_OK) break;
+            if ((e = hipMemsetAsync(dflag.ptr, 0, sizeof(unsigned long long), s)) != hipSuccess) {
+                set_error("entry cut: %s", hipGetErrorString(e));
+                st = MSH_EDEVICE;
+                break;
+            }
             if ((st = dq.reserve(n * 3 * sizeof(double))) != MSH_OK) break;
             if ((st = df.reserve(n * sizeof(uint32_t))) != MSH_OK) break;
             if ((st = dp.reserve(n * 3 * sizeof(double))) != MSH_OK) break;
@@ -626,12 +638,17 @@ static int build_entry_cut(msh_tree* t, bool fine) {
             if (kCutFromHalf && t->d_cut && 2 * t->cut_G == G && t->cut_wide == (e4 ? 0 : 1) &&
                 t->cut_lo[0] == lo[0] && t->cut_lo[1] == lo[1] && t->cut_lo[2] == lo[2])
                 half = t->d_cut;
-            if ((st = cut_level(t, G, lo, w, dp.as<double>(), dhint.as<int>(), cut, e4, s, half)) != MSH_OK) break;
+            if ((st = cut_level(t, G, lo, w, dp.as<double>(), dhint.as<int>(), cut, e4, s, half,
+                                dflag.as<unsigned long long>(), directional)) != MSH_OK)
+                break;
             (void)hipEventRecord(e1, s);
-            if ((e = hipStreamSynchronize(s)) != hipSuccess) {
+            unsigned long long nflag = 0;
+            if ((e = hipMemcpyAsync(&nflag, dflag.ptr, sizeof(nflag), hipMemcpyDeviceToHost, s)) != hipSuccess ||
+                (e = hipStreamSynchronize(s)) != hipSuccess) {
                 set_error("entry cut build: %s", hipGetErrorString(e));
                 st = MSH_EDEVICE;
             }
+            flagged = nflag;
         } while (0);
         (void)hipStreamSynchronize(s);  // the temporaries are freed (DevBuf destructors) as this scope ends
     }
@@ -639,6 +656,7 @@ static int build_entry_cut(msh_tree* t, bool fine) {
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, e0, e1);
         t->cut_ms = ms;
+        t->cut_flagged = flagged;
         t->d_cut = cut;
         t->cut_wide = e4 ? 0 : 1;
         t->cut_G = G;
@@ -701,6 +719,7 @@ static void ensure_entry_cut(msh_tree* t, size_t S) {
     uint32_t* old = t->d_cut;
     const int old_G = t->cut_G, old_wide = t->cut_wide;
     const double old_ms = t->cut_ms;
+    const uint64_t old_flagged = t->cut_flagged;
     double old_lo[3], old_iw[3];
     for (int k = 0; k < 3; ++k) {
         old_lo[k] = t->cut_lo[k];
@@ -723,6 +742,7 @@ static void ensure_entry_cut(msh_tree* t, size_t S) {
             t->cut_G = old_G;
             t->cut_wide = old_wide;
             t->cut_ms = old_ms;
+            t->cut_flagged = old_flagged;
             for (int k = 0; k < 3; ++k) {
                 t->cut_lo[k] = old_lo[k];
                 t->cut_iw[k] = old_iw[k];
@@ -1793,6 +1813,12 @@ int msh_tree_entry_cut_info(const msh_tree* t, int* state, int* G, uint64_t* byt
     if (G) *G = t->d_cut ? t->cut_G : 0;
     if (bytes) *bytes = n * (t->cut_wide ? 64 : 32);
     if (build_ms) *build_ms = t->cut_ms;
+    return MSH_OK;
+}
+
+int msh_tree_entry_cut_flagged(const msh_tree* t, uint64_t* cells) {
+    if (!t || !cells) { set_error("msh_tree_entry_cut_flagged: null argument"); return MSH_EINVAL; }
+    *cells = t->d_cut ? t->cut_flagged : 0;
     return MSH_OK;
 }
 

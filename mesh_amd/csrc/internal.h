@@ -167,6 +167,7 @@ struct msh_tree {
     int cut_fails = 0;        // failed automatic builds (retried after another threshold of rows, at most twice)
     bool cut_fine = false;    // the built grid is the fine automatic one (or a requested one): no upgrade
     double cut_ms = 0.0;
+    uint64_t cut_flagged = 0;  // cells of the built grid whose record a directional drop shortened (k_cut_level)
     double cut_lo[3] = {0, 0, 0}, cut_iw[3] = {0, 0, 0};
     msh::Workspace ws;
     // copies of this tree on the other devices of msh_set_devices / msh_set_device_list (owned; freed with it):
@@ -244,11 +245,21 @@ int unpermute_results(const QRes* d_res, const double* d_w, int nw, const uint32
 constexpr int kCutK = 7;
 constexpr uint32_t kCutEmpty = 0x7FFFFFFFu;  // empty 64-B record entry: not a node id (ids < T - 1 <= 2^31 - 2) nor a ~leaf
 constexpr size_t kEnt4MaxLeaves = (size_t)1 << 20;  // 4-B stack / cut entries: refs in [-2^20, 2^20), 21 bits
+// k_cut_level's directional drop (nearest.hip cut_dir_drop) and the mark of a record it shortened: bit 30 of word 0
+// (the hint leaf; leaves < 2^26) in 32-B records -- 64-B records zero their radius word instead.  The alongnormal
+// walks start at the root in a marked cell (rays.hip); the closest-point walks mask the bit.
+#ifndef MSH_CUT_DIRECTIONAL
+#define MSH_CUT_DIRECTIONAL 1
+#endif
+constexpr bool kCutDirectional = MSH_CUT_DIRECTIONAL != 0;
+constexpr uint32_t kCutDirFlag = 0x40000000u;
 int cut_centres(int G, const double* lo, const double* w, double* d_q, hipStream_t s);
 // d_half: the records of the G/2 grid over the same box (same record size), each cell then starts from its enclosing
-// half-resolution cell's entries instead of the root; nullptr: from the root
+// half-resolution cell's entries instead of the root; nullptr: from the root.  directional: also apply the
+// directional drop; d_nflag (nullable): incremented by the number of records it shortened
 int cut_level(const msh_tree* tree, int G, const double* lo, const double* w, const double* d_pts, const int* d_hint,
-              uint32_t* d_rec, bool e4, hipStream_t s, const uint32_t* d_half = nullptr);
+              uint32_t* d_rec, bool e4, hipStream_t s, const uint32_t* d_half = nullptr,
+              unsigned long long* d_nflag = nullptr, bool directional = true);
 // d_inv[face] = the leaf holding it (T words)
 int face_leaf_map(const msh_tree* tree, uint32_t* d_inv, hipStream_t s);
 // closest point (and part) of each row q[i] on face d_face[i] (the traversal's answer construction); d_inv from

@@ -788,6 +788,8 @@ __device__ inline size_t cut_cell(const KnnArgs& a, const D3& q) {
 // the cell's record: word 0 its hint leaf (-1: none), then kCutK entries nearest-first -- 4-B entries in the stack's
 // own packing (Ent4: the bound's top 11 bits over a 21-bit ref; empty entries have the sign bit set) in a 32-B
 // record, or (ref, bound bits) pairs from word 2 of a 64-B record (empty: ref kCutEmpty)
+// (kCutDirFlag in word 0: a directional drop shortened the list, internal.h -- the closest-point walks only mask it)
+__device__ inline int cut_hint_leaf(uint32_t w0) { return (int)w0 < 0 ? -1 : (int)(w0 & ~kCutDirFlag); }
 __device__ inline const uint32_t* cut_rec(const KnnArgs& a, size_t cell) {
     return a.cut + cell * (a.cut_wide ? 16 : 8);
 }
@@ -929,14 +931,14 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
         const size_t cell = kList && fin ? cut_cell(a, q) : kNoCell;
         if constexpr (kLean) {
             if (cell != kNoCell) {  // the cell's hint leaf, as below
-                const int lf = (int)a.cut[cell * 8];
+                const int lf = cut_hint_leaf(a.cut[cell * 8]);
                 if (lf >= 0) pol.test(lf);
             }
         } else if constexpr (MODE == 0 || MODE == 3) {
             if (kList && a.cut && cell != kNoCell && a.phase != 2) {
                 // slots without a leader (super-leaders, leaders, unled launches) inside the grid: the cell's hint
                 // leaf (the closest face found for its centre), within U(c) + r of q's own answer
-                const int lf = (int)cut_rec(a, cell)[0];
+                const int lf = cut_hint_leaf(cut_rec(a, cell)[0]);
                 if (STATS) hint_leaf = lf;
                 if (lf >= 0) {
                     pol.test(lf);
@@ -950,7 +952,7 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
                 if (STATS) hint_leaf = lf;
 #if MSH_FOLLOW_CELL
                 // followers inside the grid also test their cell's hint leaf (one call site: a loop of two)
-                const int lc = (kList && a.cut && cell != kNoCell) ? (int)cut_rec(a, cell)[0] : -1;
+                const int lc = (kList && a.cut && cell != kNoCell) ? cut_hint_leaf(cut_rec(a, cell)[0]) : -1;
 #pragma nounroll
                 for (int j = 0; j < 2; ++j) {
                     const int h = j == 0 ? lf : (lc != lf ? lc : -1);
@@ -2103,12 +2105,88 @@ __global__ __launch_bounds__(kBlock) void k_cut_centres(int G, double lx, double
 // list covers, then (ref, bound bits) pairs): word 0 the hint leaf, then the entries nearest-first with max(s, 0)^2
 // rounded down to fp32, s = sqrt(bound) (1 - 1e-5) - r (1 + 1e-5): a lower bound of the squared distance from any q
 // of the cell.
-template <bool E4>
+//
+// The directional drop (cut_dir_drop).  The ball rule is the triangle inequality on two distances from c; it ignores
+// that, as q moves in the cell, the distance to a box B and the distance to c's closest point pc move almost together.
+// Let a_k (k = 0, 1, 2) be the node's fp32 frame rows (n, t, b = n x t as frame_b rounds it) taken as exact reals, A
+// the matrix of these rows, o the tree origin, and B = {x : lo_k <= a_k . (x - o) <= hi_k} the child's decoded box: a
+// convex set that contains every vertex below the child (build.hip projects the fp64 vertices on these same widened
+// axes and rounds every bound outward by at least an fp32 ulp, which covers its own fp64 roundings; looser is safe).
+// With y = A (x - o) the box is axis-aligned, and since lambda_max(A A^T) <= 1 + 1e-6 (node_child_bounds; this is all
+// the rule asks of the frame: neither unit rows nor right angles), |A v| <= (1 + 1e-6)^(1/2) |v|, hence
+//   dist(x, B) >= k D(x),  D(x) = the distance from A (x - o) to the axis-aligned box [lo, hi],  k = 1 - 1e-6.
+// Take F(x) = k D(x) - |x - pc| <= dist(x, B) - |x - pc|.  Where D > 0 and x != pc it is differentiable with
+//   grad F(x) = k A^T u(x) - v(x),  u = g / |g| (g the signed slab-gap vector of A (x - o)),  v = (x - pc) / |x - pc|.
+// g is 1-Lipschitz in y (y minus its projection on a convex set) and normalising costs at most a factor 2 / length
+// (|a/|a| - b/|b|| <= 2 |a - b| / max(|a|, |b|)), so along the segment from c to any x with |x - c| = s <= r
+//   |grad F(x) - grad F(c)| <= 2 k lambda_max s / D(c) + 2 s / |c - pc| <= 4 s / d_B + 2 s / d_p,
+// d_B = D(c), d_p = |c - pc|, provided D > 0 and x != pc on the segment: D(x) >= d_B - (1 + 1e-6) r and
+// |x - pc| >= d_p - r, so the rule is tried only when d_B > r (1 + 1e-5) and d_p > r (1 + 1e-5).  Integrating,
+//   F(q) >= F(c) - r (|grad F(c)| + 4 r / d_B + 2 r / d_p)   for every q within r of c
+// (every q of the cell: r is its half-diagonal + 0.1 %, which also covers the rounding of cut_cell's cell index).
+// When the right side exceeds the margin m > 0, every q of the cell has
+//   dist(q, any face below the child) >= dist(q, B) >= F(q) + |q - pc| > |q - pc| + m >= d(q) + m:
+// the subtree holds neither q's answer nor a tie, and the walk's result is unchanged bit for bit.
+// The margin m = 2^-40 (|c - o|_1 + |pc - o|_1 + d_B + d_p) stands for everything computed rather than exact: the
+// left side is ~40 fp64 operations on operands no larger than those four magnitudes, each rounding <= 2^-53 of
+// them (no cancellation is relied on: the differences are bounded by the operands), so its error is < 2^-46 of the
+// sum; pc is the centre walk's fp64 construction, within a few 2^-53 |pc - o| of a true mesh point; and the walks
+// compare squared distances computed to a few 2^-53 relative, so a face farther by m > 2^-41 d(q) can neither win
+// nor tie in their arithmetic.  The inequality is strict.  The test is OR-ed with the ball rule (it only drops
+// children the ball rule kept), the stored entry bounds keep their formula, and a fine cell may still start from
+// its coarse cell's record: a drop proved for every q of the coarse cell holds for the fine cell's.
+// The alongnormal walks (rays.hip k_rays<0>) read a record as "every face within R of c is below the list", which a
+// directional drop breaks: such a record is flagged -- kCutDirFlag in word 0 of a 32-B record, word 1 (the radius) 0
+// in a 64-B one -- and inherits the flag of the coarse record it starts from; a ray in a flagged cell starts at the
+// root.  The closest-point walks mask the flag (cut_hint_leaf).  nflag: the number of flagged cells.
+// Both children at once (they share the frame and c's projections); h0 / h1: in, the child passed the ball rule; out,
+// it also survives this one.  r2p = 2 r^2 / d_p.  Returns whether a child was dropped.
+__device__ inline bool cut_dir_drop(const NodeV& nd, bool& h0, bool& h1, const D3& co, const D3& vp, double dp, double r,
+                                    double r2p, double mag) {
+    float ax[3][3], e0[6], e1[6];
+    nd.frame(ax[0], ax[1], ax[2]);
+    nd.extents(e0, e1);
+    double p[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[k] = (double)ax[k][0] * co.x + (double)ax[k][1] * co.y + (double)ax[k][2] * co.z;
+    const double kf = 1.0 - 1e-6;
+    bool dropped = false;
+#pragma unroll
+    for (int side = 0; side < 2; ++side) {
+        bool& h = side ? h1 : h0;
+        if (!h) continue;
+        const float* e = side ? e1 : e0;
+        double g[3], d2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double lo = (double)e[k], hi = (double)e[3 + k];
+            g[k] = p[k] < lo ? p[k] - lo : (p[k] > hi ? p[k] - hi : 0.0);
+            d2 += g[k] * g[k];
+        }
+        const double dB = sqrt(d2);
+        if (!(dB > r * (1.0 + 1e-5))) continue;       // also NaN / a non-finite box
+        if (!(kf * dB - dp - r2p > 0.0)) continue;    // the common case near the foot point: no gradient needed
+        const double inv = 1.0 / dB, ks = kf * inv;
+        const D3 w = D3{ks * ((double)ax[0][0] * g[0] + (double)ax[1][0] * g[1] + (double)ax[2][0] * g[2]) - vp.x,
+                        ks * ((double)ax[0][1] * g[0] + (double)ax[1][1] * g[1] + (double)ax[2][1] * g[2]) - vp.y,
+                        ks * ((double)ax[0][2] * g[0] + (double)ax[1][2] * g[1] + (double)ax[2][2] * g[2]) - vp.z};
+        const double lhs = kf * dB - dp - r * (sqrt(vdot(w, w)) + 4.0 * r * inv) - r2p;
+        if (lhs > 9.094947017729282e-13 * (mag + dB)) {  // 2^-40
+            h = false;
+            dropped = true;
+        }
+    }
+    return dropped;
+}
+// DIR: with the directional drop (its fp64 work doubles the kernel's registers, so the ball-rule-only launches of the
+// automatic coarse grid keep their own instantiation: C3 3.7 ms against 5.0 ms as a launch argument).
+template <bool E4, bool DIR>
 __global__ __launch_bounds__(kBlock) void k_cut_level(const BNode* __restrict__ nodes, const TriRec* __restrict__ tris,
                                                       double ox, double oy, double oz, double tm, int G, double lx,
                                                       double ly, double lz, double wx, double wy, double wz,
                                                       const double* __restrict__ pts, const int* __restrict__ hint,
-                                                      uint32_t* __restrict__ rec, const uint32_t* __restrict__ crec) {
+                                                      uint32_t* __restrict__ rec, const uint32_t* __restrict__ crec,
+                                                      unsigned long long* __restrict__ nflag) {
     constexpr int kw = E4 ? 8 : 16;  // record words
     // a wave takes a 4 x 4 x 4 brick of cells (bricks in row order): its cells' start lists share their nodes, and
     // under a half-resolution grid it reads 8 records
@@ -2133,10 +2211,19 @@ __global__ __launch_bounds__(kBlock) void k_cut_level(const BNode* __restrict__ 
     // U(c): the distance from c to its answer's point (pts: the centre walks' closest points; NaN without an answer)
     const D3 pc = D3{pts[3 * cell], pts[3 * cell + 1], pts[3 * cell + 2]};
     float limf = INFINITY;
+    const double dp = sqrt(sqdist(c, pc));
     {
-        const double R = (sqrt(sqdist(c, pc)) + 2.0 * r) * (1.0 + 1e-6);
+        const double R = (dp + 2.0 * r) * (1.0 + 1e-6);
         if (R < INFINITY) limf = __double2float_ru(R * R * kSlack);  // NaN / inf (no answer): the root only
     }
+    // the directional drop's constants (cut_dir_drop): c and pc relative to the origin, v = (c - pc) / d_p
+    const D3 co = D3{c.x - ox, c.y - oy, c.z - oz};
+    const bool dir = DIR && dp > r * (1.0 + 1e-5) && dp < INFINITY;
+    const float dp2f = __double2float_rd(dp * dp);
+    const D3 vp = D3{(c.x - pc.x) / dp, (c.y - pc.y) / dp, (c.z - pc.z) / dp};
+    const double mag = fabs(co.x) + fabs(co.y) + fabs(co.z) + fabs(pc.x - ox) + fabs(pc.y - oy) + fabs(pc.z - oz) + dp;
+    const double r2p = 2.0 * r * r / dp;
+    bool flagged = false;  // a directional drop removed what the ball rule kept (here or in the coarse record)
     if (crec) {
         // start from the enclosing cell of the half-resolution grid (G = 2 Gc, the same box): a subtree its record left
         // out lies farther than d(q) from every q of that cell, this one's included.  Its entries keep their records'
@@ -2144,6 +2231,7 @@ __global__ __launch_bounds__(kBlock) void k_cut_level(const BNode* __restrict__ 
         // maps back to <= sqrt(b); a node's bound is raised when it is loaded
         const size_t Gc = (size_t)G / 2;
         const uint32_t* cr = crec + (((iz >> 1) * Gc + (iy >> 1)) * Gc + (ix >> 1)) * kw;
+        flagged = E4 ? ((int)cr[0] >= 0 && (cr[0] & kCutDirFlag)) : cr[1] == 0u;
         m = 0;
         for (int k = 0; k < kCutK; ++k) {
             uint32_t rv, bb;
@@ -2183,7 +2271,10 @@ __global__ __launch_bounds__(kBlock) void k_cut_level(const BNode* __restrict__ 
                 float d0, d1;
                 node_child_bounds(nd, qf, d0, d1);
                 bd[k] = fmaxf(bd[k], fminf(d0, d1));
-                const bool h0 = d0 <= limf, h1 = d1 <= limf;
+                bool h0 = d0 <= limf, h1 = d1 <= limf;
+                // (a child whose fp32 bound is within d_p^2 is not tried: the rule needs d_B > d_p; skipping is safe)
+                if (dir && ((h0 && d0 > dp2f) || (h1 && d1 > dp2f)) && cut_dir_drop(nd, h0, h1, co, vp, dp, r, r2p, mag))
+                    flagged = true;
                 const int cnt = (int)h0 + (int)h1;
                 if (m - 1 + cnt > kCutK) {
                     stuck[k] = m;
@@ -2231,10 +2322,17 @@ __global__ __launch_bounds__(kBlock) void k_cut_level(const BNode* __restrict__ 
             bd[j - 1] = tb;
         }
     uint32_t* out = rec + cell * kw;
-    out[0] = (uint32_t)best_leaf;
+    out[0] = (uint32_t)best_leaf | (E4 && flagged && best_leaf >= 0 ? kCutDirFlag : 0u);
     // 64-B records: word 1 the radius R around c the list covers (every subtree left out lies farther from c), fp32
-    // rounded down (0: none) -- the alongnormal walks' first phase reads it (rays.hip)
-    if (!E4) out[1] = limf < INFINITY ? __float_as_uint(__double2float_rd(sqrt((double)limf / kSlack) * (1.0 - 1e-7))) : 0u;
+    // rounded down (0: none, or a flagged record) -- the alongnormal walks' first phase reads it (rays.hip)
+    if (!E4)
+        out[1] = limf < INFINITY && !flagged
+                     ? __float_as_uint(__double2float_rd(sqrt((double)limf / kSlack) * (1.0 - 1e-7)))
+                     : 0u;
+    if (nflag) {
+        const unsigned long long fl = __ballot(flagged);
+        if (flagged && (unsigned)__ffsll((long long)fl) - 1u == ln) atomicAdd(nflag, (unsigned long long)__popcll(fl));
+    }
     for (int k = 0; k < kCutK; ++k) {
         uint32_t ev = 0xFFFFFFFFu, rv = kCutEmpty, bb = 0u;
         if (k < m) {
@@ -2331,18 +2429,21 @@ int cut_centres(int G, const double* lo, const double* w, double* d_q, hipStream
 }
 
 int cut_level(const msh_tree* tree, int G, const double* lo, const double* w, const double* d_pts, const int* d_hint,
-              uint32_t* d_rec, bool e4, hipStream_t s, const uint32_t* d_half) {
+              uint32_t* d_rec, bool e4, hipStream_t s, const uint32_t* d_half, unsigned long long* d_nflag,
+              bool directional) {
     const size_t GB = ((size_t)G + 3) / 4;  // 4^3-cell bricks, one per wave
     const unsigned nb = (unsigned)((GB * GB * GB * 64 + kBlock - 1) / kBlock);
     const TriRec* tris = static_cast<const TriRec*>(tree->d_leaves);
     const double tm = tree_margin(tree->half_diag);
     TimedLaunch tl("cut_level", s);
-    if (e4)
-        k_cut_level<true><<<nb, kBlock, 0, s>>>(tree->d_nodes, tris, tree->origin[0], tree->origin[1], tree->origin[2], tm,
-                                               G, lo[0], lo[1], lo[2], w[0], w[1], w[2], d_pts, d_hint, d_rec, d_half);
+    auto launch = [&](auto kern) {
+        kern<<<nb, kBlock, 0, s>>>(tree->d_nodes, tris, tree->origin[0], tree->origin[1], tree->origin[2], tm, G, lo[0], lo[1],
+                                   lo[2], w[0], w[1], w[2], d_pts, d_hint, d_rec, d_half, d_nflag);
+    };
+    if (directional && kCutDirectional)
+        e4 ? launch(k_cut_level<true, true>) : launch(k_cut_level<false, true>);
     else
-        k_cut_level<false><<<nb, kBlock, 0, s>>>(tree->d_nodes, tris, tree->origin[0], tree->origin[1], tree->origin[2], tm,
-                                                G, lo[0], lo[1], lo[2], w[0], w[1], w[2], d_pts, d_hint, d_rec, d_half);
+        e4 ? launch(k_cut_level<true, false>) : launch(k_cut_level<false, false>);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }

@@ -685,8 +685,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MODE == 
                 if (ux >= 0.0 && ux < G && uy >= 0.0 && uy < G && uz >= 0.0 && uz < G) {
                     const unsigned ix = (unsigned)ux, iy = (unsigned)uy, iz = (unsigned)uz;
                     const uint32_t* r = a.cut + (((size_t)iz * a.cut_G + iy) * a.cut_G + ix) * (a.cut_wide ? 16 : 8);
+                    // a record shortened by a directional drop (k_cut_level) does not cover that ball: from the root
+                    // (32-B records carry kCutDirFlag; 64-B ones a zero radius, so rr <= 0 below)
                     const int hint = (int)r[0];
-                    if (hint >= 0) {
+                    if (hint >= 0 && !((uint32_t)hint & kCutDirFlag)) {
                         const D3 c = D3{a.cut_lo[0] + ((double)ix + 0.5) / a.cut_iw[0],
                                         a.cut_lo[1] + ((double)iy + 0.5) / a.cut_iw[1],
                                         a.cut_lo[2] + ((double)iz + 0.5) / a.cut_iw[2]};

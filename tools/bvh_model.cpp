@@ -665,8 +665,30 @@ ObbTree make_obb_tree(const double* v, const uint32_t* f, int T) {
     }
     return t;
 }
+// closest point of triangle (a, b, c) to p (Ericson, Real-Time Collision Detection 5.1.5)
+void tri_closest(const double* p, const double* a, const double* b, const double* c, double* out) {
+    auto dot = [](const double* x, const double* y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; };
+    double ab[3], ac[3], ap[3], bp[3], cp[3];
+    for (int k = 0; k < 3; ++k) { ab[k] = b[k] - a[k]; ac[k] = c[k] - a[k]; ap[k] = p[k] - a[k]; bp[k] = p[k] - b[k]; cp[k] = p[k] - c[k]; }
+    auto set = [&](double vv, double ww) { for (int k = 0; k < 3; ++k) out[k] = a[k] + vv * ab[k] + ww * ac[k]; };
+    const double d1 = dot(ab, ap), d2 = dot(ac, ap);
+    if (d1 <= 0 && d2 <= 0) return set(0, 0);
+    const double d3 = dot(ab, bp), d4 = dot(ac, bp);
+    if (d3 >= 0 && d4 <= d3) return set(1, 0);
+    const double vc = d1 * d4 - d3 * d2;
+    if (vc <= 0 && d1 >= 0 && d3 <= 0) return set(d1 / (d1 - d3), 0);
+    const double d5 = dot(ab, cp), d6 = dot(ac, cp);
+    if (d6 >= 0 && d5 <= d6) return set(0, 1);
+    const double vb = d5 * d2 - d1 * d6;
+    if (vb <= 0 && d2 >= 0 && d6 <= 0) return set(0, d2 / (d2 - d6));
+    const double va = d3 * d6 - d5 * d4;
+    if (va <= 0 && d4 - d3 >= 0 && d5 - d6 >= 0) { const double w = (d4 - d3) / ((d4 - d3) + (d5 - d6)); return set(1 - w, w); }
+    const double den = 1.0 / (va + vb + vc);
+    set(vb * den, vc * den);
+}
 // nodes loaded by a near-first traversal from the given start nodes with initial squared bound b0;
-// returns final best
+// returns final best (g_walk_face: the face that gave it, when one improved on b0)
+thread_local int g_walk_face = -1;
 double walk(const ObbTree& t, const double* v, const uint32_t* f, const double* q, const std::vector<int>& start,
             double b0, uint32_t& nn, uint32_t& nl, uint64_t* hist) {
     double best = b0;
@@ -693,7 +715,8 @@ double walk(const ObbTree& t, const double* v, const uint32_t* f, const double* 
                 if (h[s] && n.c[s] < 0) {
                     int fc = t.tr.order[~n.c[s]];
                     const uint32_t* ff = f + 3 * fc;
-                    best = std::min(best, tri_d2(q, v + 3 * ff[0], v + 3 * ff[1], v + 3 * ff[2]));
+                    const double td = tri_d2(q, v + 3 * ff[0], v + 3 * ff[1], v + 3 * ff[2]);
+                    if (td < best) { best = td; g_walk_face = fc; }
                     ++nl;
                     h[s] = false;
                 }
@@ -735,6 +758,83 @@ std::vector<int> cell_cut(const ObbTree& t, const double* c, double lim, int dcu
         cur.swap(nxt);
     }
     return cur;
+}
+// the directional drop of nearest.hip k_cut_level: with pc the closest point of the centre c, d_p = |c - pc|, d_B the
+// distance from c to the box and u_B, u_p the unit vectors from the box's nearest point and from pc to c, every q
+// within r of c has dist(q, B) - |q - pc| >= d_B - d_p - r (|u_B - u_p| + 4 r / d_B + 2 r / d_p)
+bool dir_drop(const double* c, const double* pc, double r, const OBB& o) {
+    double g[3] = {0, 0, 0};
+    for (int a = 0; a < 3; ++a) {
+        const double p = c[0] * o.ax[a][0] + c[1] * o.ax[a][1] + c[2] * o.ax[a][2];
+        const double ga = p < o.lo[a] ? p - o.lo[a] : (p > o.hi[a] ? p - o.hi[a] : 0.0);
+        for (int k = 0; k < 3; ++k) g[k] += ga * o.ax[a][k];
+    }
+    const double dB = std::sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+    const double e[3] = {c[0] - pc[0], c[1] - pc[1], c[2] - pc[2]};
+    const double dp = std::sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+    if (!(dB > r && dp > r)) return false;
+    double du = 0;
+    for (int k = 0; k < 3; ++k) du += (g[k] / dB - e[k] / dp) * (g[k] / dB - e[k] / dp);
+    return dB - dp - r * (std::sqrt(du) + 4 * r / dB + 2 * r / dp) > 1e-9 * (dB + dp);
+}
+// start list of a cell as k_cut_level forms it: entries (nodes, or ~leaves, which are final) are replaced by their
+// children within lim of c in passes over the list while it keeps at most K entries; an entry that cannot be expanded
+// is retried once the list has shrunk.  pc (nullable): also drop the children dir_drop proves useless for the cell.
+// stuck_out: 1 when the expansion ended with an internal entry that did not fit.
+std::vector<int> cell_cut_list(const ObbTree& t, const double* c, double lim, int K, const double* pc, double r,
+                               int* stuck_out) {
+    std::vector<int> ref{0}, stuck{0};
+    for (int pass = 0; pass < 256; ++pass) {
+        bool changed = false;
+        const int m0 = (int)ref.size();
+        for (int k = 0; k < m0 && k < (int)ref.size(); ++k) {
+            const int m = (int)ref.size();
+            if (ref[k] < 0) continue;
+            if (stuck[k] && m >= stuck[k]) continue;
+            const int x = ref[k];
+            bool h[2];
+            for (int s = 0; s < 2; ++s)
+                h[s] = obb_d2(c, t.ob[2 * x + s]) <= lim && !(pc && dir_drop(c, pc, r, t.ob[2 * x + s]));
+            const int cnt = (int)h[0] + (int)h[1];
+            if (m - 1 + cnt > K) { stuck[k] = m; continue; }
+            changed = true;
+            if (cnt == 0) {
+                ref[k] = ref.back(); stuck[k] = stuck.back();
+                ref.pop_back(); stuck.pop_back();
+                continue;
+            }
+            stuck[k] = 0;
+            const int c0 = t.tr.nodes[x].c[0], c1 = t.tr.nodes[x].c[1];
+            if (h[0]) {
+                ref[k] = c0;
+                if (h[1]) { ref.push_back(c1); stuck.push_back(0); }
+            } else {
+                ref[k] = c1;
+            }
+        }
+        if (!changed || ref.empty()) break;
+    }
+    if (stuck_out) {
+        *stuck_out = 0;
+        for (size_t k = 0; k < ref.size(); ++k)
+            if (ref[k] >= 0 && stuck[k]) *stuck_out = 1;
+    }
+    if (ref.empty()) ref.push_back(0);
+    return ref;
+}
+// walk() from a start list that may hold ~leaf entries: those are tested first (a leaf test each, no node visit)
+double walk_from(const ObbTree& t, const double* v, const uint32_t* f, const double* q, const std::vector<int>& start,
+                 double b0, uint32_t& nn, uint32_t& nl) {
+    double best = b0;
+    std::vector<int> nodes;
+    for (int e : start) {
+        if (e >= 0) { nodes.push_back(e); continue; }
+        const uint32_t* ff = f + 3 * t.tr.order[~e];
+        best = std::min(best, tri_d2(q, v + 3 * ff[0], v + 3 * ff[1], v + 3 * ff[2]));
+        ++nl;
+    }
+    if (nodes.empty()) return best;
+    return walk(t, v, f, q, nodes, best, nn, nl, nullptr);
 }
 }  // namespace
 
@@ -779,6 +879,52 @@ extern "C" void model_entry_cut(const double* v, const uint32_t* f, int T, const
     }
     if (depth_hist)
         for (int k = 0; k < 64; ++k) depth_hist[k] = hist[k];
+}
+
+// The start lists of k_cut_level on a G^3 grid over [blo, bhi] (at most K entries per cell, expansion in passes), with
+// the ball rule alone (rule 0) or with the directional drop as well (rule 1).  Per query inside the grid: nodes loaded
+// and leaf tests of the walk from its cell's list with a near-perfect initial bound (d* (1 + 1e-9)), the list's size,
+// and whether the expansion ended stuck on the cap.  Queries outside the grid get the walk from the root.
+extern "C" void model_cut_rule(const double* v, const uint32_t* f, int T, const double* q, long S, const double* blo,
+                               const double* bhi, int G, int K, int rule, uint32_t* cut_nodes, uint32_t* cut_leaves,
+                               uint32_t* cut_size, uint32_t* cut_stuck) {
+    ObbTree t = make_obb_tree(v, f, T);
+#pragma omp parallel for schedule(dynamic, 64)
+    for (long i = 0; i < S; ++i) {
+        const double* qq = q + 3 * i;
+        const double d2 = exact_d2(t, v, f, qq);
+        double c[3], r2 = 0;
+        bool inside = true;
+        for (int k = 0; k < 3; ++k) {
+            const double w = (bhi[k] - blo[k]) / G;
+            int ci = (int)std::floor((qq[k] - blo[k]) / w);
+            if (ci < 0 || ci >= G) inside = false;
+            ci = std::min(std::max(ci, 0), G - 1);
+            c[k] = blo[k] + (ci + 0.5) * w;
+            r2 += 0.25 * w * w;
+        }
+        uint32_t cn = 0, cl = 0;
+        if (!inside) {
+            walk(t, v, f, qq, std::vector<int>{0}, d2 * (1 + 1e-9), cn, cl, nullptr);
+            cut_nodes[i] = cn; cut_leaves[i] = cl; cut_size[i] = 0; cut_stuck[i] = 0;
+            continue;
+        }
+        const double r = std::sqrt(r2) * 1.001;
+        // the centre's closest point: the nearest face's point
+        double pc[3], dc2 = std::numeric_limits<double>::infinity();
+        {
+            uint32_t a = 0, b = 0;
+            dc2 = walk(t, v, f, c, std::vector<int>{0}, dc2, a, b, nullptr);
+            const uint32_t* ff = f + 3 * g_walk_face;
+            tri_closest(c, v + 3 * ff[0], v + 3 * ff[1], v + 3 * ff[2], pc);
+        }
+        const double dc = std::sqrt(dc2);
+        const double lim = (dc + 2 * r) * (dc + 2 * r) * (1 + 1e-9);
+        int st = 0;
+        std::vector<int> cut = cell_cut_list(t, c, lim, K, rule ? pc : nullptr, r, &st);
+        walk_from(t, v, f, qq, cut, d2 * (1 + 1e-9), cn, cl);
+        cut_nodes[i] = cn; cut_leaves[i] = cl; cut_size[i] = (uint32_t)cut.size(); cut_stuck[i] = (uint32_t)st;
+    }
 }
 
 // ---- follower hint experiment: slots in Morton order; every 8th slot is a leader answered exactly; the

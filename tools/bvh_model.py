@@ -33,8 +33,52 @@ def counts(v, f, q, kind=0):
     return nn, nl, d.value
 
 
+def cut_rule(v, f, q, G, rule, K=7, widen=1.25):
+    """model_cut_rule: per query, nodes loaded and leaf tests of the walk from its cell's start list (k_cut_level's
+    expansion; rule 0 the ball rule, 1 with the directional drop), the list's size and whether it ended stuck."""
+    L = load()
+    v = np.ascontiguousarray(v, np.float64)
+    f = np.ascontiguousarray(f, np.uint32)
+    q = np.ascontiguousarray(q, np.float64)
+    S = q.shape[0]
+    mid, half = 0.5 * (v.max(0) + v.min(0)), 0.5 * (v.max(0) - v.min(0))
+    half = widen * np.maximum(half, 0.05 * half.max())
+    blo, bhi = np.ascontiguousarray(mid - half), np.ascontiguousarray(mid + half)
+    out = [np.zeros(S, np.uint32) for _ in range(4)]
+    P = ctypes.c_void_p
+    L.model_cut_rule(P(v.ctypes.data), P(f.ctypes.data), ctypes.c_int(f.shape[0]), P(q.ctypes.data), ctypes.c_long(S),
+                     P(blo.ctypes.data), P(bhi.ctypes.data), ctypes.c_int(G), ctypes.c_int(K), ctypes.c_int(rule),
+                     *[P(o.ctypes.data) for o in out])
+    return out
+
+
+def cut_rule_bands(freq=224, n=20000, grids=(200, 400)):
+    """python tools/bvh_model.py cut-rule [freq] [rows]: C3's predicted node visits per band of |r - 1| (the bands of
+    scripts/cut_shell_probe.py), ball rule against directional rule, one JSON line per grid and rule."""
+    import json
+    import workloads as W
+    v, f = W.geodesic_icosphere(freq)
+    q = W.c3_stream(n, "cpu").numpy()
+    d = np.abs(np.linalg.norm(q, axis=1) - 1.0)
+    bands = (0.0, 0.01, 0.02, 0.05, 0.1, 0.2, 0.4, 10.0)
+    for G in grids:
+        for rule in (0, 1):
+            nn, nl, size, stuck = cut_rule(v, f, q, G, rule)
+            rec = {"G": G, "rule": "directional" if rule else "ball", "rows": n, "nodes": float(nn.mean()),
+                   "leaves": float(nl.mean()), "entries": float(size.mean()), "stuck": float(stuck.mean()), "bands": []}
+            for lo, hi in zip(bands[:-1], bands[1:]):
+                m = (d >= lo) & (d < hi)
+                rec["bands"].append({"band": [lo, hi], "frac": float(m.mean()), "nodes": float(nn[m].mean()),
+                                     "leaves": float(nl[m].mean()), "entries": float(size[m].mean()),
+                                     "stuck": float(stuck[m].mean())})
+            print(json.dumps(rec), flush=True)
+
+
 if __name__ == "__main__":
     import workloads as W
+    if len(sys.argv) > 1 and sys.argv[1] == "cut-rule":
+        cut_rule_bands(*(int(x) for x in sys.argv[2:4]))
+        sys.exit(0)
     freq = int(sys.argv[1]) if len(sys.argv) > 1 else 224
     v, f = W.geodesic_icosphere(freq)
     q = np.random.default_rng(3).uniform(-1.1, 1.1, (20000, 3))
