@@ -13,7 +13,7 @@
 //   (k_unpermute).  Unsorted launches read and write the caller's arrays directly.
 //
 // Execution shape (gfx950):
-//   Pass 1 (k_knn): persistent grid; each WAVE dequeues 64-query tiles from one of 8 XCD-group
+//   Pass 1 (k_knn, k_knn_lean): persistent grid; each WAVE dequeues 64-query tiles from one of 8 XCD-group
 //     counters (group = blockIdx % 8 labels the blocks sharing an XCD; each counter owns a contiguous
 //     eighth of the Morton-sorted queries, so an XCD's L2 serves one region of the BVH; exhausted
 //     groups steal).  One lane per query, near-child-first depth-first traversal: one 64-B node read
@@ -24,7 +24,7 @@
 //     Aila & Laine, dealt to every lane of the wave).  Pass 1 runs over super-leader slots, then leader
 //     slots, then followers, each starting from the leaf of its nearest leader's answer.
 //     The fp32 pruning radius is cached per lane and refreshed only when the best distance changes.
-//     The cut-started unled launch of a sorted call (the headline) runs the lean instantiation (MSH_KNN_LEAN).
+//     The cut-started unled launch of a sorted call (the headline) runs k_knn_lean.
 //     A lane that exceeds `budget` node steps stops and appends its query (with its exact best so far)
 //     to a deferred list: queries near the centre of a closed surface are equidistant from most of it
 //     and would otherwise hold their whole wave for ~10^6 steps.
@@ -35,6 +35,10 @@
 //     lanes' own stacks for depth-first walks.
 // Ties: the lexicographic minimum of (squared distance, face index) — deterministic and independent of
 // traversal order or of how the work was split (every box within best*(1+2^-40) is visited).
+// Retired A/B switches (their shipped sides are the code; records under profiles/): MSH_TILE_PF
+// (r06_c3_tile_prefetch_ab.jsonl), MSH_RESUME (r05_ab_leaders_sort_resume.jsonl), MSH_KNN_LEAN, MSH_LEAN_COLD,
+// MSH_LEAN_STEP and MSH_LEAN_STATE (r07_c3_knn_lean_ab.jsonl, r07_knn_lean_isa.txt), and MSH_FOLLOW_CELL (followers
+// also testing their cell's hint leaf: never shipped, no record kept).
 #include <algorithm>
 #include <cstddef>
 #include <cstdlib>
@@ -413,7 +417,7 @@ struct WalkerT {
         if (PF && r && node >= 0) node_prefetch(nodes, node, wsl);
         return r;
     }
-    // step_collect<PF = true> of the lean pass-1 kernel (k_knn LEAN).  The caller keeps two ring places free, so
+    // step_collect<PF = true> of the lean pass-1 kernel (k_knn_lean).  The caller keeps two ring places free, so
     // both leaf children are always handed back and no leaf is parked by the step itself (`node < 0` still enters:
     // cut records hold ~leaf refs).  One wave-uniform test covers the deep stack: when no lane of the step holds
     // kStack entries or more, the push writes LDS (index sp < kStack) and every pop reads it (indices < sp <= kStack),
@@ -532,7 +536,7 @@ __device__ inline void write_result(const KnnArgs& a, size_t i, const D3& q, con
     }
 }
 
-// write_result of the lean pass-1 kernel (k_knn LEAN): the sorted path's direct stores to the caller's row r, and
+// write_result of the lean pass-1 kernel (k_knn_lean): the sorted path's direct stores to the caller's row r, and
 // nothing else (no slot-order record, no unsorted form).
 template <int MODE, class Pol>
 __device__ inline void write_direct(const TriRec* __restrict__ tris, size_t r, const D3& q, const Pol& pol,
@@ -572,15 +576,7 @@ __device__ inline T cold_arg(size_t off) {
     asm volatile("" : "+s"(p));
     return *(__attribute__((address_space(4))) const T*)(p + off);
 }
-// (MSH_LEAN_COLD 0: the plain by-value field of the kernel's `a`, for the A/B)
-#ifndef MSH_LEAN_COLD
-#define MSH_LEAN_COLD 1
-#endif
-#if MSH_LEAN_COLD
 #define MSH_COLD_ARG(f) cold_arg<decltype(KnnArgs::f)>(offsetof(KnnArgs, f))
-#else
-#define MSH_COLD_ARG(f) (a.f)
-#endif
 
 template <int MODE>
 struct PolOf { using T = TriPol; };
@@ -624,16 +620,10 @@ __device__ inline D3 load_q(const KnnArgs& a, size_t i) {
 // slots; super-leaders run first and unhinted, leaders take their hint from the kLWin super-leaders of their
 // window (4: -1.1 %), followers from the leaders of their kFWin-slot window (32: +-0, 128: -3 %).
 #ifndef MSH_KLEAD
-#define MSH_KLEAD 8
+#define MSH_KLEAD 8  // at least 2, and a divisor of kLead2 (launch_knn always runs leader phases where they apply)
 #endif
 #ifndef MSH_KFWIN
 #define MSH_KFWIN 64
-#endif
-#ifndef MSH_FOLLOW_CELL
-#define MSH_FOLLOW_CELL 0
-#endif
-#ifndef MSH_RESUME
-#define MSH_RESUME 1
 #endif
 constexpr unsigned kLead = MSH_KLEAD;
 constexpr unsigned kLead2 = 256;
@@ -708,52 +698,14 @@ __device__ inline unsigned lanes_below(unsigned long long m) {
 #define MSH_KPEND 32
 #endif
 constexpr int kPend = MSH_KPEND;
-// Tile prefetch (round 6): a wave claims its next tile while the current one's rows load.  dequeue_tile is two
-// dependent round trips to the group's counter (a load, then the atomic), paid at every tile start with the wave
-// idle: C3 100M pass 1 38.4-39.5 -> 36.3-36.4 ms, 2.35-2.41 -> 2.53-2.54 G q/s; the 12.5M shard 6.92-6.95 -> 6.76-6.78
-// ms (profiles/r06_c3_tile_prefetch_ab.jsonl)
-#ifndef MSH_TILE_PF
-#define MSH_TILE_PF 1
-#endif
-
-// Lean pass-1 kernel (k_knn LEAN): the headline launch -- every slot in one unled launch, started from a narrow entry
-// cut, direct stores -- gets an instantiation without the leader / follower starts, the T == 1 path, wide cut
-// records, slot-order records and the inv_w store.  80 SGPR spills (lanes of two VGPRs, read back inside the wave
-// loop) -> 3, none in the loop; 8 VGPR spills -> 2; 9,500 -> 3,100 instructions (profiles/r07_knn_lean_isa.txt).
-// C3 100M, G q/s, builds interleaved in one session each (profiles/r07_c3_knn_lean_ab.jsonl):
-//   generic kernel (parent)                          2.543 2.547 2.591 | 2.569 2.574 2.572 | 2.559 2.541 2.531 2.533 2.533
-//   lean, dead paths out only (STEP 0, COLD 0)       2.498 2.502 2.523   (38 SGPR spills; slower than the parent)
-//   + MSH_LEAN_COLD: cold arguments read where used  2.533 2.562 2.537
-//   + MSH_LEAN_STEP: step_list, two ring places kept 2.599 2.598 2.596 | 2.594 2.594 2.600 | 2.586 2.563 2.557 2.552 2.557
-//   + MSH_LEAN_STATE: walk state in one VGPR                                                | 2.588 2.589 2.588 2.587 2.591
-// and a fifth session of six runs each: parent 2.533-2.557; lean with cold arguments only 2.420-2.496; + step_list
-// 2.544-2.564; + packed state 2.592-2.610 (the state's slowest run 1.1 % over the fastest without it, whose runs spread
-// by 0.8 %; step and state together 3.8 % over the build without either, whose runs spread by 3.2 %).
-// MSH_LEAN_COLD: the deferral, resume, spill-area and output arguments are read from the kernarg segment after the
-// tile's wave loop (cold_arg) instead of living in SGPRs across it.  MSH_LEAN_STEP: the node step without the
-// park-the-farther-leaf branch (a lane walks while two ring places are free) and with the deep-stack case behind one
-// wave-uniform test (WalkerT::step_list).  MSH_LEAN_STATE: active / want_defer / deferred as one per-lane register
-// instead of three lane masks kept by ~25 scalar instructions per iteration.  Each 0 restores the generic form inside
-// the lean kernel, for the A/B; MSH_KNN_LEAN 0: every launch runs the generic kernel.
-// Rejected (same sessions): a 4-B load of each appended leaf's record into a register nothing reads, so that its round
-// finds it in cache -- 2.496 when the next step's vmcnt(0) waits for it, 2.505-2.510 (one load per iteration) and
-// 2.465-2.470 (two) when the step's wait leaves them in flight: the rounds' loads are not what the wave waits for, and
-// the extra vector-memory instructions cost 3-5 %.  Loading the next round's triangle before the current round's
-// fp64 work needs 20 more VGPRs than the 2 the kernel has left.
-#ifndef MSH_KNN_LEAN
-#define MSH_KNN_LEAN 1
-#endif
+// Tile prefetch: a wave claims its next tile while the current one's rows load, instead of paying dequeue_tile's two
+// dependent round trips at every tile start with the wave idle (C3 100M pass 1 38.4-39.5 -> 36.3-36.4 ms,
+// profiles/r06_c3_tile_prefetch_ab.jsonl).
 // MSH_LIST_RESERVE 1 (a counting build, not shipped): the generic list kernel keeps the two ring places free too, so
 // its step never parks a leaf and it visits what the lean kernel visits; instrumented launches (msh_tree_nearest_stats)
 // run the generic kernel, and this is how the reserve's effect on the node and leaf counts is measured.
 #ifndef MSH_LIST_RESERVE
 #define MSH_LIST_RESERVE 0
-#endif
-#ifndef MSH_LEAN_STEP
-#define MSH_LEAN_STEP 1
-#endif
-#ifndef MSH_LEAN_STATE
-#define MSH_LEAN_STATE 1
 #endif
 
 constexpr unsigned kRing = 256;     // ring entries per wave: < 64 left after full rounds + <= 128 per step
@@ -851,15 +803,11 @@ __device__ inline bool cut_start_narrow(const uint32_t* __restrict__ cut, size_t
 // (node_prefetch); the 16 KB the node slots take per block come out of the stack.  C3: 1889 -> 1945 M q/s in one
 // session, wave-cycles waiting on memory 55.7 -> 46.7 % at +10 VALU instructions per query
 // (profiles/r04_c3_node_prefetch_lds_ab.jsonl).
-template <int MODE, bool STATS, bool LIST, bool PF, bool LEAN = false>
+template <int MODE, bool STATS, bool LIST, bool PF>
 __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
     constexpr bool kCompact = MODE == 0 || MODE == 3;  // per-lane queues dealt to the wave (else: per-lane rounds)
     constexpr bool kList = (MODE == 0 || MODE == 3) && LIST;  // a separate instantiation: its own registers
     constexpr bool kPF = kList && PF;  // 4-B stack entries and nodes prefetched into LDS
-    constexpr bool kLean = LEAN;       // the cut-started unled launch only (launch_knn's pass1; MSH_KNN_LEAN)
-    constexpr bool kLeanStep = LEAN && MSH_LEAN_STEP;  // with the straighter node step (step_list)
-    constexpr bool kLeanState = LEAN && MSH_LEAN_STATE;  // with the lane's walk state packed in one register
-    static_assert(!LEAN || (kPF && !STATS), "the lean kernel is a list-path, prefetching, uninstrumented one");
     typedef typename std::conditional<kPF, Ent4, Ent8>::type E;
     __shared__ typename E::T stk[kStack * kBlock];
     __shared__ float4 nbuf[kPF ? 4 * kBlock : 1];
@@ -875,66 +823,41 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
     const uint32_t wsl = (uint32_t)(size_t)(__attribute__((address_space(3))) float4*)(nbuf + (kPF ? wv_u * 256 : 0));
     const float4* nb = nbuf + (kPF ? (tid >> 6) * 256 + lane : 0);
     uint2* ent = lent + (kCompact ? (tid >> 6) * 64 * kLeafQ : 0);
-    // (lean: the spill column is worked out where a deep stack needs it, lean_spill below)
-    uint2* spill = (!kLeanStep && a.spill) ? a.spill + (size_t)blockIdx.x * kBlock * (size_t)a.spill_depth + tid : nullptr;
+    uint2* spill = a.spill ? a.spill + (size_t)blockIdx.x * kBlock * (size_t)a.spill_depth + tid : nullptr;
     const unsigned group = blockIdx.x & 7u;
     unsigned long long u_trav_it = 0, u_trav_lanes = 0, u_leaf_it = 0, u_leaf_lanes = 0;  // STATS: wave iterations
     unsigned n_nodes = 0, n_leaves = 0;
     unsigned n_impr = 0, n_hinted = 0, n_hint_won = 0;  // STATS: improving leaf tests, hinted queries, hint = answer
-#if MSH_TILE_PF
     // lane 0 claims the wave's next tile of its own group while the current one's rows load (an atomic whose return
     // is waited for with the tile's first loads), instead of at the next tile's start
     const unsigned glo = (unsigned)(((unsigned long long)a.ntiles * group) >> 3);
     const unsigned ghi = (unsigned)(((unsigned long long)a.ntiles * (group + 1)) >> 3);
     unsigned nxt = ~0u;
-#endif
     for (;;) {
         unsigned tile = 0;
-#if MSH_TILE_PF
         if (lane == 0) tile = (nxt != ~0u && glo + nxt < ghi) ? glo + nxt : dequeue_tile(a.counters, a.ntiles, group);
-#else
-        if (lane == 0) tile = dequeue_tile(a.counters, a.ntiles, group);
-#endif
         tile = __shfl(tile, 0);
         if (tile >= a.ntiles) break;
         // every lane of the wave stays in the tile's loops (compacted leaf phases deal entries to all 64 lanes);
         // a lane without a query (past the phase's units, or a non-finite row) only helps
         const size_t k = (size_t)tile * 64 + lane;
         size_t i = 0;
-        bool live = k < (kLean ? a.S : a.nunits);  // lean: phase 0, every slot
+        bool live = k < a.nunits;
         if (live) {
-            i = kLean ? k : slot_of(a, k);
+            i = slot_of(a, k);
             live = i < a.S;
         }
         const D3 q = live ? load_q(a, i) : D3{0.0, 0.0, 0.0};
-#if MSH_TILE_PF
         if (lane == 0) nxt = glo < ghi ? atomicAdd(&a.counters[group * 32], 1u) : ~0u;
-#endif
-        if constexpr (!kLean)
-            if (live && a.inv_w && !a.direct) a.inv_w[a.qperm[i]] = (uint32_t)i;
+        if (live && a.inv_w && !a.direct) a.inv_w[a.qperm[i]] = (uint32_t)i;
         auto pol = make_pol<MODE>(a, i, q);
         const bool fin = live && finite3(q);
-        // lean: the sorted path's direct stores to the caller's row, their arguments fetched here (cold_arg)
-        auto lean_write = [&]() {
-            if constexpr (kLean)
-                write_direct<MODE>(static_cast<const TriRec*>(a.leaves), (size_t)MSH_COLD_ARG(perm)[i], q, pol,
-                                   MSH_COLD_ARG(out_face), MSH_COLD_ARG(out_part), MSH_COLD_ARG(out_pt),
-                                   MSH_COLD_ARG(out_w));
-        };
         if (live && !fin) {  // no distance is defined: NO_FACE / NaN, no traversal
-            if constexpr (kLean)
-                lean_write();
-            else if (!STATS || a.res)
-                write_result<MODE>(a, i, q, pol);
+            if (!STATS || a.res) write_result<MODE>(a, i, q, pol);
         }
         int hint_leaf = -1;  // STATS
         const size_t cell = kList && fin ? cut_cell(a, q) : kNoCell;
-        if constexpr (kLean) {
-            if (cell != kNoCell) {  // the cell's hint leaf, as below
-                const int lf = cut_hint_leaf(a.cut[cell * 8]);
-                if (lf >= 0) pol.test(lf);
-            }
-        } else if constexpr (MODE == 0 || MODE == 3) {
+        if constexpr (MODE == 0 || MODE == 3) {
             if (kList && a.cut && cell != kNoCell && a.phase != 2) {
                 // slots without a leader (super-leaders, leaders, unled launches) inside the grid: the cell's hint
                 // leaf (the closest face found for its centre), within U(c) + r of q's own answer
@@ -950,19 +873,6 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
             } else if (fin && (a.phase == 2 || a.phase == 1)) {
                 const int lf = a.phase == 2 ? leader_leaf(a, i, q, kFWin, kLead) : leader_leaf(a, i, q, kLWin * kLead2, kLead2);
                 if (STATS) hint_leaf = lf;
-#if MSH_FOLLOW_CELL
-                // followers inside the grid also test their cell's hint leaf (one call site: a loop of two)
-                const int lc = (kList && a.cut && cell != kNoCell) ? cut_hint_leaf(cut_rec(a, cell)[0]) : -1;
-#pragma nounroll
-                for (int j = 0; j < 2; ++j) {
-                    const int h = j == 0 ? lf : (lc != lf ? lc : -1);
-                    if (h >= 0) {
-                        pol.test(h);
-                        if (STATS) ++n_leaves;
-                    }
-                }
-                if (STATS && lf >= 0) ++n_hinted;
-#else
                 if (lf >= 0) {
                     pol.test(lf);
                     if (STATS) {
@@ -970,10 +880,9 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
                         ++n_hinted;
                     }
                 }
-#endif
             }
         }
-        if (!kLean && a.T == 1) {
+        if (a.T == 1) {
             if (fin) {
                 pol.test(0);
                 if (STATS) ++n_leaves;
@@ -984,42 +893,21 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
         if constexpr (kList) {
           {
             QF qf;
-            int root = 0;
-            if constexpr (kLean) {  // single tree
-                const double o[3] = {a.org[0], a.org[1], a.org[2]};
-                qf = make_qf(q, o, a.tm);
-            } else {
-                root = query_root(a, i, q, qf);
-            }
+            const int root = query_root(a, i, q, qf);
             WalkerT<E> w{root, 0};
             bool start = fin;
-            if constexpr (kLeanStep) {
-                if (cell != kNoCell) start = cut_start_narrow(a.cut, cell, pol, w, lds);
-            } else {
-                if (cell != kNoCell) start = cut_start(a, cell, pol, w, lds, spill);
-            }
-            auto lean_spill = [&]() -> uint2* {
-                return MSH_COLD_ARG(spill) + (size_t)blockIdx.x * kBlock * (size_t)MSH_COLD_ARG(spill_depth) + tid;
-            };
+            if (cell != kNoCell) start = cut_start(a, cell, pol, w, lds, spill);
             if (kPF && start && w.node >= 0) node_prefetch(a.nodes, w.node, wsl);
             uint32_t* ring = lsh + (tid >> 6) * (kRing + 64 * 4);
             unsigned long long* bd = reinterpret_cast<unsigned long long*>(ring + kRing);  // per owner: d2 bits
             unsigned long long* bfl = bd + 64;                                              // (face << 32 | leaf)
             bool active = start, want_defer = false, deferred = false;
-            // lean (kLeanState): the three flags as one VGPR -- 0 idle, 1 walking, 2 past its budget (its own leaves
-            // still wait), 3 deferred -- instead of three lane masks the compiler updates with scalar code at every
-            // iteration
-            enum { kIdle = 0, kWalk = 1, kPast = 2, kDeferred = 3 };
-            int st = start ? kWalk : kIdle;
             int nq = 0;              // this lane's leaves appended since all of them were last evaluated (a bound)
             unsigned last_pos = 0;   // ring counter of this lane's newest entry
             unsigned head = 0, tail = 0;  // wave-uniform ring counters: entries [head, tail) wait
             unsigned steps = 0;
             const unsigned max_steps = (unsigned)min(a.T, (size_t)UINT_MAX);
-            unsigned budget = a.budget;
-            // lean: held in an SGPR (left alone, the compiler reloads it from the kernarg segment at every step and
-            // waits for it)
-            if constexpr (kLean) asm volatile("" : "+s"(budget));
+            const unsigned budget = a.budget;
             unsigned tot = 0;  // STATS: node steps of this lane, restarts included
             // Evaluate ring entries [head, upto) in rounds of 64, one per lane: each lane tests its entry's leaf
             // against its owner's query (ds_bpermute); the owners publish their best before each round and take
@@ -1065,29 +953,19 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
                 if ((int)(last_pos - head) < 0) nq = 0;  // every entry of this lane is evaluated
             };
             unsigned dslot = ~0u;  // this lane's deferred-list slot (deferred)
-          lean_again:
             for (;;) {
                 // a lane past its budget defers once its own leaves are evaluated (pass 2 then owns the query); its
                 // records are written after the tile's loop, so the loop holds no copy of the construction
-                if constexpr (kLeanState) {
-                    if (st == kPast && nq == 0) st = kDeferred;
-                } else if (want_defer && nq == 0) {
+                if (want_defer && nq == 0) {
                     want_defer = false;
-                    if constexpr (kLean) {  // its slot is claimed after the loop, with the list's arguments
+                    dslot = atomicAdd(a.n_deferred, 1u);
+                    if (dslot < a.max_deferred) {
                         active = false;
                         deferred = true;
-                    } else {
-                        dslot = atomicAdd(a.n_deferred, 1u);
-                        if (dslot < a.max_deferred) {
-                            active = false;
-                            deferred = true;
-                        }
-                        // deferred list full: finish here without a budget
                     }
+                    // deferred list full: finish here without a budget
                 }
-                // lean: two ring places stay free, so a step hands back both leaf children (step_list)
-                const bool can = (kLeanState ? st == kWalk : active && !want_defer) &&
-                                 nq < ((kLeanStep || MSH_LIST_RESERVE) ? kPend - 1 : kPend);
+                const bool can = active && !want_defer && nq < (MSH_LIST_RESERVE ? kPend - 1 : kPend);
                 const bool any = __ballot(can) != 0ull;
                 if (!any && tail == head) break;  // nothing queued and nobody can move: the tile is done
                 if (STATS) {
@@ -1099,19 +977,12 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
                 }
                 int l0 = -1, l1 = -1;
                 if (can) {
-                    if constexpr (kLeanStep)
-                        active = w.step_list(a.nodes, qf, pol, lds, lean_spill, l0, l1, nb, wsl);
-                    else
-                        active = w.template step_collect<decltype(pol), STATS, kPF>(a.nodes, qf, pol, lds, spill,
-                                                                                      n_nodes, l0, l1, kPend - nq, nb,
-                                                                                      wsl);
+                    active = w.template step_collect<decltype(pol), STATS, kPF>(a.nodes, qf, pol, lds, spill, n_nodes,
+                                                                                  l0, l1, kPend - nq, nb, wsl);
                     ++steps;
                     if (STATS) ++tot;
                     if (active && steps >= max_steps) active = false;  // each node is entered once: corrupt tree
-                    if constexpr (kLeanState)  // (the flags stay out of it: `active` is this step's result only)
-                        st = !active ? kIdle : (steps == budget ? kPast : kWalk);
-                    else if (active && steps == budget)
-                        want_defer = true;
+                    if (active && steps == budget) want_defer = true;
                 }
                 // append this step's leaves (at most two per lane) to the ring, in lane order
                 if (l0 < 0) {
@@ -1135,57 +1006,7 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
                 const unsigned upto = any ? head + ((tail - head) & ~63u) : tail;
                 if (upto != head) run_rounds(upto);
             }
-            if constexpr (kLean) {
-                // claim the deferred lanes' list slots; with the list full a lane takes its walk up again where it
-                // stopped (its pending node is still prefetched), now without a budget: steps is past it
-                bool again = false;
-                const unsigned max_deferred = MSH_COLD_ARG(max_deferred);
-                if constexpr (kLeanState) deferred = st == kDeferred;
-                if (deferred && dslot == ~0u) {
-                    dslot = atomicAdd(MSH_COLD_ARG(n_deferred), 1u);
-                    if (dslot >= max_deferred) {
-                        deferred = false;
-                        active = true;
-                        st = kWalk;
-                        again = true;
-                    }
-                }
-                if (__ballot(again) != 0ull) goto lean_again;
-                // only a lane that holds a slot of the list is deferred: steps is past the budget after a refused
-                // claim, so neither form of the walk state asks to defer a second time
-                deferred = deferred && dslot < max_deferred;
-            }
-            if constexpr (kLean) {
-              if (deferred) {
-                DeferRec r;
-                r.slot = (uint32_t)i;
-                r.face = pol.best_face;
-                r.leaf = pol.best_leaf;
-                r.roff = 0;
-                r.best = pol.best;
-                r.rcnt = 0;
-                r.sbound = 0x7F800000u;  // +inf
-                unsigned long long* const max_best = MSH_COLD_ARG(max_best);
-                if (max_best) atomicMax(max_best, (unsigned long long)__double_as_longlong(pol.best));
-                uint2* const resume = MSH_COLD_ARG(resume);
-                if (resume) {
-                    const unsigned cnt = (unsigned)w.sp + 1;
-                    const unsigned off = atomicAdd(MSH_COLD_ARG(n_resume), cnt);
-                    if (off + cnt <= MSH_COLD_ARG(resume_cap)) {
-                        uint2* dst = resume + off;
-                        const uint2* sp_col = w.sp > kStack ? lean_spill() : nullptr;
-                        for (int j = 0; j < w.sp; ++j) {
-                            const typename E::T e = stack_get(lds, sp_col, j);
-                            dst[j] = make_uint2((uint32_t)E::ref(e), __float_as_uint(E::bound(e)));
-                        }
-                        dst[w.sp] = make_uint2((uint32_t)w.node, 0u);
-                        r.roff = off;
-                        r.rcnt = cnt;
-                    }
-                }
-                MSH_COLD_ARG(deferred)[dslot] = r;
-              }
-            } else if (deferred) {
+            if (deferred) {
                 if ((a.phase == 1 || a.phase == 3 || a.phase == 4) && a.res) {
                     // later phases take hints from this slot before pass 2 answers it: publish the closest point of
                     // the best face so far (a point on the mesh), or NO_FACE when it has none yet
@@ -1246,11 +1067,7 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
             }
             if (STATS && fin && hint_leaf >= 0 && pol.best_leaf == hint_leaf) ++n_hint_won;
             if (deferred) continue;
-            if constexpr (kLean) {
-                if (fin) lean_write();
-            } else {
-                if (fin && (!STATS || a.res)) write_result<MODE>(a, i, q, pol);
-            }
+            if (fin && (!STATS || a.res)) write_result<MODE>(a, i, q, pol);
             continue;
           }
         }
@@ -1450,6 +1267,215 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
             atomicAdd(&a.stats[5], u_leaf_lanes);
         }
     }
+}
+
+// Lean pass-1 kernel: the headline launch -- phase 0 over every slot of a sorted call, a single tree of > 1 and
+// <= 2^20 leaves with a narrow entry cut, direct stores (launch_knn's pass1 checks all of it).  It is k_knn's list
+// path with the node prefetch, written out without the leader / follower starts, the T == 1 path, wide cut records,
+// slot-order records, the inv_w store and the instrumented counters.  Its cold arguments are read from the kernarg
+// segment after the tile's wave loop (cold_arg), its node step keeps two ring places free and puts the deep stack
+// behind one wave-uniform test (WalkerT::step_list), and a lane's walk state is one register.  Against k_knn: 80 SGPR
+// spills -> 3, none in the loop; C3 100M 2.533-2.557 -> 2.592-2.610 G q/s (profiles/r07_knn_lean_isa.txt,
+// r07_c3_knn_lean_ab.jsonl).  The ring code (run_rounds, the append) is k_knn's, statement for statement.
+template <int MODE>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MSH_KNN_WAVES))) void k_knn_lean(KnnArgs a) {
+    static_assert(MODE == 0 || MODE == 3, "closest-point modes");
+    typedef Ent4 E;
+    __shared__ uint32_t stk[kStack * kBlock];
+    __shared__ float4 nbuf[4 * kBlock];
+    __shared__ uint32_t lsh[4 * (kRing + 64 * 4)];  // per wave: ring + bd/bfl (u64 per lane each)
+    const int tid = threadIdx.x, lane = tid & 63;
+    uint32_t* lds = stk + tid;
+    // the wave's node slots: LDS byte address from a wave-uniform wave index, so M0 is set by scalar code
+    const int wv_u = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t wsl = (uint32_t)(size_t)(__attribute__((address_space(3))) float4*)(nbuf + wv_u * 256);
+    const float4* nb = nbuf + (tid >> 6) * 256 + lane;
+    const unsigned group = blockIdx.x & 7u;
+    // the tile claim with its prefetch, as in k_knn
+    const unsigned glo = (unsigned)(((unsigned long long)a.ntiles * group) >> 3);
+    const unsigned ghi = (unsigned)(((unsigned long long)a.ntiles * (group + 1)) >> 3);
+    unsigned nxt = ~0u;
+    for (;;) {
+        unsigned tile = 0;
+        if (lane == 0) tile = (nxt != ~0u && glo + nxt < ghi) ? glo + nxt : dequeue_tile(a.counters, a.ntiles, group);
+        tile = __shfl(tile, 0);
+        if (tile >= a.ntiles) break;
+        const size_t k = (size_t)tile * 64 + lane;  // phase 0: unit k is slot k
+        size_t i = 0;
+        bool live = k < a.S;
+        if (live) {
+            i = k;
+            live = i < a.S;
+        }
+        const D3 q = live ? load_q(a, i) : D3{0.0, 0.0, 0.0};
+        if (lane == 0) nxt = glo < ghi ? atomicAdd(&a.counters[group * 32], 1u) : ~0u;
+        auto pol = make_pol<MODE>(a, i, q);
+        const bool fin = live && finite3(q);
+        // the sorted path's direct stores to the caller's row, their arguments fetched here (cold_arg)
+        auto write = [&]() {
+            write_direct<MODE>(static_cast<const TriRec*>(a.leaves), (size_t)MSH_COLD_ARG(perm)[i], q, pol,
+                               MSH_COLD_ARG(out_face), MSH_COLD_ARG(out_part), MSH_COLD_ARG(out_pt),
+                               MSH_COLD_ARG(out_w));
+        };
+        if (live && !fin) write();  // no distance is defined: NO_FACE / NaN, no traversal
+        const size_t cell = fin ? cut_cell(a, q) : kNoCell;
+        if (cell != kNoCell) {  // the cell's hint leaf (the closest face found for its centre)
+            const int lf = cut_hint_leaf(a.cut[cell * 8]);
+            if (lf >= 0) pol.test(lf);
+        }
+        QF qf;
+        const double o[3] = {a.org[0], a.org[1], a.org[2]};  // single tree
+        qf = make_qf(q, o, a.tm);
+        WalkerT<E> w{0, 0};
+        bool start = fin;
+        if (cell != kNoCell) start = cut_start_narrow(a.cut, cell, pol, w, lds);
+        // the lane's global spill column, worked out only where a deep stack needs it
+        auto spill_col = [&]() -> uint2* {
+            return MSH_COLD_ARG(spill) + (size_t)blockIdx.x * kBlock * (size_t)MSH_COLD_ARG(spill_depth) + tid;
+        };
+        if (start && w.node >= 0) node_prefetch(a.nodes, w.node, wsl);
+        uint32_t* ring = lsh + (tid >> 6) * (kRing + 64 * 4);
+        unsigned long long* bd = reinterpret_cast<unsigned long long*>(ring + kRing);  // per owner: d2 bits
+        unsigned long long* bfl = bd + 64;                                              // (face << 32 | leaf)
+        bool active = start, deferred = false;  // (active: the last step's result only)
+        // the lane's walk state, one VGPR (three lane masks would be kept by scalar code at every iteration): idle,
+        // walking, past its budget (its own leaves still wait), deferred
+        enum { kIdle = 0, kWalk = 1, kPast = 2, kDeferred = 3 };
+        int st = start ? kWalk : kIdle;
+        int nq = 0;              // this lane's leaves appended since all of them were last evaluated (a bound)
+        unsigned last_pos = 0;   // ring counter of this lane's newest entry
+        unsigned head = 0, tail = 0;  // wave-uniform ring counters: entries [head, tail) wait
+        unsigned steps = 0;
+        const unsigned max_steps = (unsigned)min(a.T, (size_t)UINT_MAX);
+        unsigned budget = a.budget;
+        // held in an SGPR (left alone, the compiler reloads it from the kernarg segment at every step and waits for it)
+        asm volatile("" : "+s"(budget));
+        auto run_rounds = [&](unsigned upto) {  // k_knn's, without the counters
+            while (head != upto) {
+                const unsigned n = min(64u, upto - head);
+                bd[lane] = (unsigned long long)__double_as_longlong(pol.best);
+                bfl[lane] = ~0ull;
+                const bool valid = (unsigned)lane < n;
+                const uint32_t en = ring[(head + (valid ? (unsigned)lane : 0u)) & (kRing - 1)];
+                const int src = (int)(en & 63u);
+                const int leaf = (int)(en >> 6);
+                const D3 x = D3{__shfl(pol.q.x, src), __shfl(pol.q.y, src), __shfl(pol.q.z, src)};
+                uint32_t f;
+                const double d2 = pol.eval(leaf, x, f);
+                const unsigned long long kb = (unsigned long long)__double_as_longlong(d2);
+                asm volatile("" ::: "memory");
+                if (valid) atomicMin(&bd[src], kb);
+                asm volatile("" ::: "memory");
+                if (valid && bd[src] == kb) atomicMin(&bfl[src], ((unsigned long long)f << 32) | (unsigned)leaf);
+                asm volatile("" ::: "memory");
+                const unsigned long long nb = bd[lane], nf = bfl[lane];
+                const double nd = __longlong_as_double((long long)nb);
+                const uint32_t nface = (uint32_t)(nf >> 32);
+                if (nf != ~0ull && (nd < pol.best || (nd == pol.best && nface < pol.best_face))) {
+                    pol.best = nd;
+                    pol.best_face = nface;
+                    pol.best_leaf = (int)(uint32_t)nf;
+                    pol.relim();
+                }
+                asm volatile("" ::: "memory");
+                head += n;
+            }
+            if ((int)(last_pos - head) < 0) nq = 0;  // every entry of this lane is evaluated
+        };
+        unsigned dslot = ~0u;  // this lane's deferred-list slot
+    walk:
+        for (;;) {
+            // a lane past its budget defers once its own leaves are evaluated (pass 2 then owns the query); its slot is
+            // claimed and its records are written after the loop, so the loop holds no copy of the construction
+            if (st == kPast && nq == 0) st = kDeferred;
+            // two ring places stay free, so a step hands back both leaf children (step_list)
+            const bool can = st == kWalk && nq < kPend - 1;
+            const bool any = __ballot(can) != 0ull;
+            if (!any && tail == head) break;  // nothing queued and nobody can move: the tile is done
+            int l0 = -1, l1 = -1;
+            if (can) {
+                active = w.step_list(a.nodes, qf, pol, lds, spill_col, l0, l1, nb, wsl);
+                ++steps;
+                if (active && steps >= max_steps) active = false;  // each node is entered once: corrupt tree
+                st = !active ? kIdle : (steps == budget ? kPast : kWalk);
+            }
+            // append this step's leaves (at most two per lane) to the ring, in lane order
+            if (l0 < 0) {
+                l0 = l1;
+                l1 = -1;
+            }
+            const unsigned long long m1 = __ballot(l0 >= 0), m2 = __ballot(l1 >= 0);
+            const unsigned pos = tail + lanes_below(m1) + lanes_below(m2);
+            if (l0 >= 0) {
+                ring[pos & (kRing - 1)] = ((uint32_t)l0 << 6) | (uint32_t)lane;
+                last_pos = pos;
+                ++nq;
+            }
+            if (l1 >= 0) {
+                ring[(pos + 1) & (kRing - 1)] = ((uint32_t)l1 << 6) | (uint32_t)lane;
+                last_pos = pos + 1;
+                ++nq;
+            }
+            tail += (unsigned)(__popcll(m1) + __popcll(m2));
+            // full rounds while lanes can move; everything once nobody can
+            const unsigned upto = any ? head + ((tail - head) & ~63u) : tail;
+            if (upto != head) run_rounds(upto);
+        }
+        {
+            // claim the deferred lanes' list slots; with the list full a lane takes its walk up again where it
+            // stopped (its pending node is still prefetched), now without a budget: steps is past it
+            bool again = false;
+            const unsigned max_deferred = MSH_COLD_ARG(max_deferred);
+            deferred = st == kDeferred;
+            if (deferred && dslot == ~0u) {
+                dslot = atomicAdd(MSH_COLD_ARG(n_deferred), 1u);
+                if (dslot >= max_deferred) {
+                    deferred = false;
+                    active = true;
+                    st = kWalk;
+                    again = true;
+                }
+            }
+            if (__ballot(again) != 0ull) goto walk;
+            // only a lane that holds a slot of the list is deferred: steps is past the budget after a refused claim,
+            // so the walk state does not ask to defer a second time
+            deferred = deferred && dslot < max_deferred;
+        }
+        if (deferred) {  // the record that hands the slot to pass 2, and what is left of the walk (as in k_knn)
+            DeferRec r;
+            r.slot = (uint32_t)i;
+            r.face = pol.best_face;
+            r.leaf = pol.best_leaf;
+            r.roff = 0;
+            r.best = pol.best;
+            r.rcnt = 0;
+            r.sbound = 0x7F800000u;  // +inf
+            unsigned long long* const max_best = MSH_COLD_ARG(max_best);
+            if (max_best) atomicMax(max_best, (unsigned long long)__double_as_longlong(pol.best));
+            uint2* const resume = MSH_COLD_ARG(resume);
+            if (resume) {
+                const unsigned cnt = (unsigned)w.sp + 1;
+                const unsigned off = atomicAdd(MSH_COLD_ARG(n_resume), cnt);
+                if (off + cnt <= MSH_COLD_ARG(resume_cap)) {
+                    uint2* dst = resume + off;
+                    const uint2* sp_col = w.sp > kStack ? spill_col() : nullptr;
+                    for (int j = 0; j < w.sp; ++j) {
+                        const uint32_t e = stack_get(lds, sp_col, j);
+                        dst[j] = make_uint2((uint32_t)E::ref(e), __float_as_uint(E::bound(e)));
+                    }
+                    dst[w.sp] = make_uint2((uint32_t)w.node, 0u);
+                    r.roff = off;
+                    r.rcnt = cnt;
+                }
+            }
+            MSH_COLD_ARG(deferred)[dslot] = r;
+            continue;
+        }
+        if (fin) write();
+    }
+    // a lane that stopped (deferred) may still have a node prefetch in flight: it lands before the block's LDS is
+    // released
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 // lexicographic min of (best, face) over the wave; every lane ends with the winner
@@ -1840,7 +1866,8 @@ static int launch_knn(msh_tree* tree, KnnArgs a, hipStream_t s, const char* time
     // with the hint leaf of the cell centre, and the leader launch's hints for the followers no longer pay for the
     // launch (C3 100M: 1985-1990 -> 2150-2179 M q/s without leader phases; one N = 8 shard of 12.5M rows 9.0 ->
     // 7.55 ms, profiles/r05_ab_leaders_sort_resume.jsonl); batched trees and trees without a cut keep them
-    const bool lead = kLead > 1 && (MODE == 0 || MODE == 3) && a.res != nullptr && a.S >= 64 * (size_t)kLead &&
+    static_assert(kLead > 1 && kLead2 == 256, "the leader phases below: leaders, and super-leaders among them");
+    const bool lead = (MODE == 0 || MODE == 3) && a.res != nullptr && a.S >= 64 * (size_t)kLead &&
                       a.T >= kLeadMinLeaves && !(a.list && a.cut);
     a.max_deferred = (unsigned)std::min<size_t>(a.S, (a.S / 16) + 65536);
     // test hook: a shorter deferred list, so that a few rows past their budget fill it (a lane that finds it full
@@ -1862,17 +1889,15 @@ static int launch_knn(msh_tree* tree, KnnArgs a, hipStream_t s, const char* time
         a.cand = ws.p2cand.as<P2Cand>();
         a.heavy = reinterpret_cast<unsigned*>(a.cand + (size_t)split_cap * kP2Split);
     }
-#if MSH_RESUME
     if (a.list) {  // resume arena: ~48 entries per expected deferral (C3: 75k deferred of 100M queries), >= 1M entries
         const size_t cap = std::min<size_t>((size_t)1 << 26, std::max<size_t>((size_t)1 << 20, 48 * (a.S / 1024 + 1024)));
         MSH_TRY(ws.resume.reserve(cap * sizeof(uint2)));
         a.resume = ws.resume.as<uint2>();
         a.resume_cap = (unsigned)cap;
     }
-#endif
-    // the lean kernel takes the cut-started unled launch (k_knn LEAN); test hook MESH_AMD_KNN_LEAN=0: the generic one
+    // the lean kernel takes the cut-started unled launch (k_knn_lean); test hook MESH_AMD_KNN_LEAN=0: the generic one
     bool lean = false;
-    if constexpr (MSH_KNN_LEAN && !STATS && (MODE == 0 || MODE == 3)) {
+    if constexpr (!STATS && (MODE == 0 || MODE == 3)) {
         const char* e = getenv("MESH_AMD_KNN_LEAN");
         lean = (!e || atoi(e) != 0) && a.list && list_pf && a.cut && !a.cut_wide && a.direct && a.T > 1 &&
                !a.orgs;
@@ -1890,9 +1915,8 @@ static int launch_knn(msh_tree* tree, KnnArgs a, hipStream_t s, const char* time
         if (nblk == 0) return MSH_OK;
         const bool take_lean = lean && phase == 0;
         TimedLaunch t1(take_lean ? "knn_lean" : name, s);  // its own timer name: tests tell the two kernels apart
-        constexpr bool kCanLean = MSH_KNN_LEAN && !STATS && (MODE == 0 || MODE == 3);
-        if (take_lean) {
-            if constexpr (kCanLean) k_knn<MODE, false, true, true, true><<<nblk, kBlock, 0, s>>>(a);
+        if (take_lean) {  // (lean is false in the other modes and in instrumented launches)
+            if constexpr (!STATS && (MODE == 0 || MODE == 3)) k_knn_lean<MODE><<<nblk, kBlock, 0, s>>>(a);
         } else if (a.list)
             if (list_pf)
                 k_knn<MODE, STATS, (MODE == 0 || MODE == 3), (MODE == 0 || MODE == 3)><<<nblk, kBlock, 0, s>>>(a);
@@ -1913,14 +1937,11 @@ static int launch_knn(msh_tree* tree, KnnArgs a, hipStream_t s, const char* time
                     // hint leaders outside it: one leader launch over every leader slot (phase 4; outside the
                     // grid unhinted) instead of a super-leader launch the chip cannot fill
                     MSH_TRY(pass1(4, n_lead, STATS ? "knn_lead_stats" : "knn_lead"));
-                } else if (kLead2 > 0) {
-                    constexpr size_t l2 = kLead2 ? kLead2 : 1;
-                    const size_t n_super = (a.S + l2 - 1) / l2;
+                } else {
+                    const size_t n_super = (a.S + kLead2 - 1) / kLead2;
                     MSH_TRY(pass1(3, n_super, STATS ? "knn_lead2_stats" : "knn_lead2"));
                     MSH_HIP(hipMemsetAsync(a.counters, 0, 8 * 32 * sizeof(unsigned), s));
                     MSH_TRY(pass1(1, n_lead - n_super, STATS ? "knn_lead_stats" : "knn_lead"));
-                } else {
-                    MSH_TRY(pass1(1, n_lead, STATS ? "knn_lead_stats" : "knn_lead"));
                 }
                 MSH_HIP(hipMemsetAsync(a.counters, 0, 8 * 32 * sizeof(unsigned), s));  // group counters only
                 MSH_TRY(pass1(2, a.S - n_lead, STATS ? "knn_follow_stats" : "knn_follow"));

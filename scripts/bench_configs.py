@@ -45,10 +45,10 @@ def pmc_of(target, kernel, units):
                     "(2 FETCH_SIZE + WRITE_SIZE) KB per dispatch, gfx950 correction"}
 
 
-# pass 1 of the closest-point traversal: the lean kernel of cut-started sorted launches, the generic one, and the
-# generic one's name in profiles taken before the lean kernel existed
-PASS1_KERNELS = ("msh::k_knn<0, false, true, true, true>", "msh::k_knn<0, false, true, true, false>",
-                 "msh::k_knn<0, false, true, true>")
+# pass 1 of the closest-point traversal: the lean kernel of cut-started sorted launches and the generic one, then
+# their names in profiles taken while the lean kernel was an instantiation of k_knn
+PASS1_KERNELS = ("msh::k_knn_lean<0>", "msh::k_knn<0, false, true, true>",
+                 "msh::k_knn<0, false, true, true, true>", "msh::k_knn<0, false, true, true, false>")
 
 
 def pass1_kernel(target):

@@ -1,15 +1,24 @@
 #!/usr/bin/env python3
-"""Register-pressure check of the closest-point traversal kernel (CPU only, no GPU needed).
+"""Register-pressure check of the closest-point traversal kernels (CPU only, no GPU needed).
 
-Compiles mesh_amd/csrc/nearest.hip to gfx950 assembly (optionally with extra -D flags) and reports, for
-k_knn<MODE, false, LIST, PF, LEAN>, the register and spill counts of the code object's metadata, and what sits inside
-the tile's wave loop (found from LLVM's loop annotations as the parent of the loop with the fp64 construction): scratch (VGPR spill) instructions,
+Compiles mesh_amd/csrc/nearest.hip to gfx950 assembly (optionally with extra -D flags) and reports, for k_knn_lean<MODE>
+and k_knn<MODE, false, LIST, PF> (MODE 0 and 3), the register and spill counts of the code object's metadata, and what
+sits inside the tile's wave loop (found from LLVM's loop annotations as the parent of the loop with the fp64 construction): scratch (VGPR spill) instructions,
 lane reads and writes (v_readlane / v_writelane: SGPR spill traffic), and the static VALU / SALU / branch counts, split
 into the leaf rounds (the innermost loop that holds the fp64 construction) and the node step (the rest of the wave
 loop).  A spill reload inside that loop costs a memory round trip per iteration: A/B runs showed -13 % for two such
 reloads, so a variant with loop spills is not worth a GPU session.
 
     python scripts/isa_check.py [-DMSH_LEAF_Q=4 ...]
+
+--save FILE only writes the assembly; --diff FILE (the --save of another tree) compares the two kernel by kernel instead
+of reporting -- the .amdhsa_* block and the instruction text, comments dropped and labels renumbered -- and exits 1
+when any kernel differs.  Two compiles of one source differ only in the __hip_cuid_* symbol, so a refactor that should
+not touch the generated code shows "identical" for every kernel.  A tree from before these options gets a copy of this
+script first (it compiles the nearest.hip beside it):
+
+    cp scripts/isa_check.py ../parent/scripts/ && python ../parent/scripts/isa_check.py --save /tmp/parent.s
+    python scripts/isa_check.py --diff /tmp/parent.s
 """
 import os
 import re
@@ -90,8 +99,11 @@ def classify(ins):
     return "mem"
 
 
-def report(s, mode, lst, pf, lean):
-    name = f"_ZN3msh5k_knnILi{mode}ELb0ELb{int(lst)}ELb{int(pf)}ELb{int(lean)}EEEvNS_7KnnArgsE"
+LEAN0 = "_ZN3msh10k_knn_leanILi0EEEvNS_7KnnArgsE"  # the headline's pass-1 kernel
+
+
+def report(s, name, tag):
+    """the record of the kernel with mangled name `name`, led by the caller's tag (which kernel it is)"""
     meta = s[re.search(r"\.name:\s+" + name + r"\n", s).start():][:1500]
     # the metadata lists a kernel's keys in alphabetical order around .name
     head = s[:re.search(r"\.name:\s+" + name + r"\n", s).start()][-600:]
@@ -100,7 +112,7 @@ def report(s, mode, lst, pf, lean):
         m = re.findall(r"\." + key + r":\s+(\d+)", text)
         return int(m[-1] if text is head else m[0]) if m else None
 
-    r = dict(mode=mode, list=lst, prefetch=pf, lean=lean)
+    r = dict(tag)
     for key in ("vgpr_count", "vgpr_spill_count", "sgpr_count", "sgpr_spill_count", "private_segment_fixed_size"):
         r[key] = md(key, meta)
     r["group_segment_fixed_size"] = md("group_segment_fixed_size", head)
@@ -137,12 +149,78 @@ def report(s, mode, lst, pf, lean):
     return r
 
 
+def kernels(s):
+    """name -> normalised text of each kernel (its instructions and its .amdhsa_* block): comments dropped, the
+    kernel's own name and the .LBB labels (numbered by function and block) replaced by their order of appearance."""
+    out = {}
+    for name in re.findall(r"^\t\.amdhsa_kernel (\S+)$", s, re.M):
+        a = s.index("\n" + name + ":")
+        body = s[a:s.index(".end_amdhsa_kernel", a)].replace(name, "KERNEL")
+        lines = [t for t in (ln.split(";")[0].rstrip() for ln in body.split("\n")) if t.strip()]
+        labels = {}
+
+        def renumber(m):
+            return labels.setdefault(m.group(0), f".L{len(labels)}")
+        out[name] = [re.sub(r"\.L(?:BB|func_end)\d+(?:_\d+)?", renumber, t) for t in lines]
+    return out
+
+
+def pre_split(name):
+    """k_knn<MODE, STATS, LIST, PF, LEAN> of an assembly from before k_knn_lean was a kernel of its own, under the name
+    it has now"""
+    m = re.fullmatch(r"_ZN3msh5k_knnILi(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)EEEvNS_7KnnArgsE", name)
+    if not m:
+        return name
+    mode, stats, lst, pf, lean = m.groups()
+    if lean == "1":
+        return f"_ZN3msh10k_knn_leanILi{mode}EEEvNS_7KnnArgsE"
+    return f"_ZN3msh5k_knnILi{mode}ELb{stats}ELb{lst}ELb{pf}EEEvNS_7KnnArgsE"
+
+
+def diff(s, other):
+    """Compare every kernel of this tree's assembly with the one saved by --save from another tree; 1 if any differs."""
+    new = kernels(s)
+    with open(other) as f:
+        old = {pre_split(k): v for k, v in kernels(f.read()).items()}
+    bad = 0
+    for name in sorted(set(old) | set(new)):
+        if name not in old or name not in new:
+            what = "only in " + (other if name in old else "this tree")
+        elif old[name] == new[name]:
+            what = "identical"
+        else:
+            a, b = old[name], new[name]
+            k = next((j for j, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
+            what = f"DIFFERS: {len(a)} -> {len(b)} lines, first at line {k}"
+        bad += what != "identical"
+        print(f"{what:12s} {name}")
+    print(f"{len(new)} kernels, {bad} not identical")
+    return 1 if bad else 0
+
+
 def main():
     flags = sys.argv[1:]
+    save = other = None
+    if "--save" in flags:  # keep the assembly, for another tree's --diff
+        save = flags.pop(flags.index("--save") + 1)
+        flags.remove("--save")
+    if "--diff" in flags:
+        other = flags.pop(flags.index("--diff") + 1)
+        flags.remove("--diff")
     s = compile_asm(flags)
-    for lst, pf, lean in ((True, True, True), (True, True, False), (True, False, False), (False, False, False)):
+    if save:
+        with open(save, "w") as f:
+            f.write(s)
+        if not other:
+            return
+    if other:
+        sys.exit(diff(s, other))
+    for mode in (0, 3):
+        print(report(s, f"_ZN3msh10k_knn_leanILi{mode}EEEvNS_7KnnArgsE", dict(kernel="k_knn_lean", mode=mode)))
+    for lst, pf in ((True, True), (True, False), (False, False)):
         for mode in (0, 3):
-            print(report(s, mode, lst, pf, lean))
+            print(report(s, f"_ZN3msh5k_knnILi{mode}ELb0ELb{int(lst)}ELb{int(pf)}EEEvNS_7KnnArgsE",
+                         dict(kernel="k_knn", mode=mode, list=lst, prefetch=pf)))
 
 
 if __name__ == "__main__":

@@ -1,4 +1,4 @@
-"""The lean pass-1 kernel of cut-started closest-point launches (nearest.hip k_knn LEAN) against brute force.
+"""The lean pass-1 kernel of cut-started closest-point launches (nearest.hip k_knn_lean) against brute force.
 
 launch_knn takes the lean kernel for a sorted launch (>= 4096 rows: direct stores) of a tree with a narrow entry cut;
 MESH_AMD_KNN_LEAN=0 forces the generic kernel.  Every case runs on a mesh small enough for the exhaustive oracle to
