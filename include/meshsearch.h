@@ -87,7 +87,7 @@ int msh_set_device(int device);
 /* In-process multi-device handles (SURVEY §8(b) msh_set_devices; the reference's drop-in call
  * Mesh.closest_faces_and_points -> AabbTree.nearest, mesh.py:454-455 / search.py:26-30, has no device argument).
  * Trees built afterwards on the calling thread are built on the first device and replicated to the others
- * (blob pack + peer copy + unpack); the host-buffer entry points (msh_tree_nearest, _nearest_bary,
+ * (blob pack + peer copy + unpack); the host-buffer entry points (msh_tree_nearest, _nearest_bary, _signed_distance,
  * _nearest_alongnormal, msh_ntree_nearest, msh_points_nearest: contiguous row ranges; msh_visibility: camera
  * ranges) then split their rows over the devices, one host thread and one chunk pipeline per device, so each
  * device's host link carries its share.  Calls below 32 MB of rows stay on the first device.  The answers equal
@@ -145,6 +145,47 @@ int msh_tree_nearest_bary_device(msh_tree* tree, const double* d_q, size_t S, ui
 int msh_tree_points_from_faces_device(msh_tree* tree, const double* d_q, size_t S, const uint32_t* d_face,
                                       uint32_t* d_part, double* d_pt, void* stream);
 
+/* ---- signed distance / inside-outside (no reference counterpart) ----
+ * The sign of the distance to a closed, consistently oriented manifold mesh by the angle-weighted pseudonormal test
+ * (Baerentzen and Aanaes 2005): with p the closest point of q and N the pseudonormal of the feature p lies on -- chosen
+ * by the part code the traversal returns: 0 the face normal, 1/2/3 the sum of the two unit face normals at edge
+ * ab/bc/ca (the face's own on a boundary edge), 4/5/6 the sum over the faces around vertex a/b/c of (angle at the
+ * vertex) x (unit face normal) -- q is inside iff (q - p) . N < 0.  No rays, no parity counting.
+ *
+ * msh_tree_sign_build derives the table on the GPU from the face array the tree was built with (host, (T,3); T must
+ * be the tree's face count): half-edges sorted by (min vertex, max vertex) give the face across every edge, corner
+ * keys sorted by vertex give every vertex's faces in ascending order (no float atomics: the table is deterministic).
+ * It holds fn (T,3) f64, vpn (P,3) f64, opp (T,3) u32 and f (T,3) u32: 48 B per face + 24 B per vertex.  The build
+ * checks that every leaf's corners equal v[f[face]] exactly (MSH_EINVAL "faces do not match the tree") and that every
+ * index is < P (MSH_EINVAL), and counts what makes the sign undefined: boundary edges (one half-edge), non-manifold
+ * edges (more than two; treated as boundary), inconsistently oriented edges (two half-edges of the same direction;
+ * the opposite face is still used) and degenerate faces (zero area: a zero normal).  With all four counters zero the
+ * sign is exact; otherwise it is undefined near the offending features.  One limit: a closest point that falls exactly
+ * on a vertex while its part code names an edge uses the edge normal.
+ * Plain triangle trees only (not the normals metric, point or batched trees, nor trees built with extra faces).
+ * Calling it again replaces the table; msh_tree_free frees it; it is installed on every replica of the handle
+ * (msh_set_devices); blobs leave it out (an unpacked handle has none until msh_tree_sign_build is called on it). */
+typedef struct msh_sign_info {
+    int32_t state;                /* 0 none, 1 built */
+    uint64_t boundary_edges, nonmanifold_edges, inconsistent_edges, degenerate_faces;
+    uint64_t bytes;               /* device bytes of the table */
+    double build_ms;              /* GPU time of its build */
+} msh_sign_info;
+int msh_tree_sign_build(msh_tree* tree, const uint32_t* f, size_t T);
+int msh_tree_sign_info(const msh_tree* tree, msh_sign_info* info);
+/* msh_tree_nearest plus sdist (S,) f64 = +-sqrt((dx dx + dy dy) + dz dz), d = q - point: negative where d . N < 0
+ * (inside an outward-oriented mesh), positive otherwise, +0.0 where d is zero, NaN on rows whose face is
+ * MSH_NO_FACE (non-finite queries).  face, part and point are msh_tree_nearest's, bit for bit.  part may be NULL.
+ * MSH_EINVAL before msh_tree_sign_build. */
+int msh_tree_signed_distance(msh_tree* tree, const double* q, size_t S, double* sdist, uint32_t* face, uint32_t* part,
+                             double* pt);
+int msh_tree_signed_distance_device(msh_tree* tree, const double* d_q, size_t S, double* d_sdist, uint32_t* d_face,
+                                    uint32_t* d_part, double* d_pt, void* stream);
+/* The sign pass alone, for given (face, part, point) rows (a caller that already holds answers, such as the narrow
+ * multi-GPU exchange): d_part is required; no workspace is used.  Device pointers; asynchronous on `stream`. */
+int msh_tree_sign_from_faces_device(msh_tree* tree, const double* d_q, size_t S, const uint32_t* d_face,
+                                    const uint32_t* d_part, const double* d_pt, double* d_sdist, void* stream);
+
 /* The order in which the closest-point path visits the S query rows (d_perm[slot] = row): stable by the
  * Hilbert index of each row's cell in a 256^3 grid over the tree's scene box widened by 10 % per side (the cell is
  * the top 24 bits of the row's 30-bit Morton code, mapped to the Hilbert curve of the same cells; then 3 LDS radix
@@ -157,7 +198,7 @@ int msh_tree_query_order(msh_tree* tree, const double* d_q, size_t S, uint32_t* 
  * queries start their walks instead of the root, and so do nearest_alongnormal rays (their walk first covers that
  * radius around p, and starts again from the root only when no hit lies that near); it changes where a walk starts,
  * never an answer.  It is built lazily by a closest-point or alongnormal call of the handle (msh_tree_nearest*,
- * msh_tree_nearest_bary*, msh_tree_nearest_alongnormal*, and their _stats).  The automatic grid comes in two sizes: the
+ * msh_tree_nearest_bary*, msh_tree_signed_distance*, msh_tree_nearest_alongnormal*, and their _stats).  The automatic grid comes in two sizes: the
  * coarse one (about 8 cells per face, at most 2^23 cells: C3 G = 200, 256 MB, ~11 ms) once the handle's calls have
  * brought at least one row per 16 of its cells (C3: 500k rows; a few small calls on a large mesh walk from the root
  * instead of paying the build), the fine one (twice the coarse resolution: about 64 cells per face, C3 G = 400,

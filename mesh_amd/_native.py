@@ -47,6 +47,11 @@ SIGNATURES = [
     ("msh_tree_nearest_bary", _i, [_vp, _c_double_p, _sz, _c_u32_p, _c_double_p, _c_double_p]),
     ("msh_tree_nearest_bary_device", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("msh_tree_points_from_faces_device", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("msh_tree_sign_build", _i, [_vp, _c_u32_p, _sz]),
+    ("msh_tree_sign_info", _i, [_vp, _vp]),
+    ("msh_tree_signed_distance", _i, [_vp, _c_double_p, _sz, _c_double_p, _c_u32_p, _c_u32_p, _c_double_p]),
+    ("msh_tree_signed_distance_device", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    ("msh_tree_sign_from_faces_device", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     ("msh_tree_set_entry_cut", _i, [_vp, _i]),
     ("msh_tree_query_order", _i, [_vp, _vp, _sz, _vp, _vp]),
     ("msh_tree_entry_cut_info", _i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), _c_u64_p, ctypes.POINTER(ctypes.c_double)]),
@@ -112,6 +117,13 @@ class BlobInfo(ctypes.Structure):
                 ("n_faces", ctypes.c_uint64), ("n_main_faces", ctypes.c_uint64), ("off_vertices", ctypes.c_uint64),
                 ("off_nodes", ctypes.c_uint64), ("off_leaves", ctypes.c_uint64), ("total", ctypes.c_uint64),
                 ("node_bytes", ctypes.c_uint32), ("leaf_bytes", ctypes.c_uint32), ("origin", ctypes.c_double * 3)]
+
+
+class SignInfo(ctypes.Structure):
+    """msh_sign_info (include/meshsearch.h): state and topology counters of a tree's sign table."""
+    _fields_ = [("state", ctypes.c_int32), ("boundary_edges", ctypes.c_uint64), ("nonmanifold_edges", ctypes.c_uint64),
+                ("inconsistent_edges", ctypes.c_uint64), ("degenerate_faces", ctypes.c_uint64),
+                ("bytes", ctypes.c_uint64), ("build_ms", ctypes.c_double)]
 
 
 def _preload_single_hip_runtime():
@@ -226,11 +238,14 @@ def empty_results(*specs):
 class Handle(object):
     """Owning reference to an ``msh_tree*`` (the reference's PyCapsule, spatialsearchmodule.cpp:125)."""
 
-    __slots__ = ("ptr", "kind", "__weakref__")
+    __slots__ = ("ptr", "kind", "faces", "__weakref__")
 
-    def __init__(self, ptr, kind):
+    def __init__(self, ptr, kind, faces=None):
         self.ptr = ptr
         self.kind = kind
+        # the host face array a triangle tree was built with ((T,3) uint32, C-contiguous copy), for sign_build;
+        # None on handles that were not built from faces here (blob_unpack)
+        self.faces = faces
 
     def info(self):
         inf = TreeInfo()
@@ -257,6 +272,30 @@ class Handle(object):
         return {"state": self.CUT_STATES.get(st.value, st.value), "G": g.value, "bytes": nb.value,
                 "build_ms": ms.value, "flagged": fl.value}
 
+    def sign_build(self, f=None):
+        """msh_tree_sign_build: derive the sign table (face normals, edge adjacency, angle-weighted vertex
+        pseudonormals) from the faces the tree was built with -- f (T,3) uint32, default the handle's own copy.
+        Calling it again replaces the table.  Returns sign_info()."""
+        if f is None:
+            f = self.faces
+        if f is None:
+            raise ValueError("sign_build: this handle keeps no face array (it was unpacked from a blob): "
+                             "call sign_build(f) with the faces the tree was built with")
+        f = np.ascontiguousarray(f, dtype=np.uint32)
+        if f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError("Faces must be Tx3")
+        check(lib().msh_tree_sign_build(self.ptr, uptr(f), f.shape[0]))
+        return self.sign_info()
+
+    def sign_info(self):
+        """msh_tree_sign_info -> dict(state, boundary_edges, nonmanifold_edges, inconsistent_edges,
+        degenerate_faces, bytes, build_ms); state is "none" or "built"."""
+        inf = SignInfo()
+        check(lib().msh_tree_sign_info(self.ptr, ctypes.byref(inf)))
+        return {"state": "built" if inf.state == 1 else "none", "boundary_edges": inf.boundary_edges,
+                "nonmanifold_edges": inf.nonmanifold_edges, "inconsistent_edges": inf.inconsistent_edges,
+                "degenerate_faces": inf.degenerate_faces, "bytes": inf.bytes, "build_ms": inf.build_ms}
+
     def free(self):
         if self.ptr:
             lib().msh_tree_free(self.ptr)
@@ -282,7 +321,8 @@ def source_build_id(extra=""):
     import hashlib
     import os
     csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-    names = sorted(["sort.hip", "build.hip", "refine.hip", "nearest.hip", "rays.hip", "tritri.hip", "geometry.hip", "api.cpp",
+    names = sorted(["sort.hip", "build.hip", "refine.hip", "nearest.hip", "rays.hip", "tritri.hip", "geometry.hip", "sign.hip",
+                    "api.cpp",
                     "loaders.cpp", "common.h", "internal.h"])
     h = hashlib.sha256()
     for p in [os.path.join(csrc, n) for n in names] + [os.path.join(csrc, "..", "..", "include", "meshsearch.h")]:
@@ -336,7 +376,7 @@ def build_tree(v, f, extra_v=None, extra_f=None):
                                       uptr(extra_f), extra_f.shape[0], ctypes.byref(out)))
     else:
         check(lib().msh_tree_build(dptr(v), v.shape[0], uptr(f), f.shape[0], ctypes.byref(out)))
-    return Handle(out.value, "triangles")
+    return Handle(out.value, "triangles", np.array(f, dtype=np.uint32, order="C"))
 
 
 def build_ntree(v, f, eps):

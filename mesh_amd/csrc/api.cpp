@@ -221,13 +221,13 @@ void DevBuf::release() {
 
 void Workspace::release() {
     DevBuf* all[] = {&keys, &vals, &keys_alt, &vals_alt, &hist, &scan, &q, &n, &out_a, &out_b, &out_c, &out_d,
-                     &flags, &counters, &spill, &stats, &ranges, &qs, &ns, &inv, &res, &res_w, &resume, &p2cand};
+                     &flags, &counters, &spill, &stats, &ranges, &qs, &ns, &inv, &res, &res_w, &resume, &p2cand, &sgn};
     for (DevBuf* b : all) b->release();
 }
 
 size_t Workspace::bytes() const {
     const DevBuf* all[] = {&keys, &vals, &keys_alt, &vals_alt, &hist, &scan, &q, &n, &out_a, &out_b, &out_c, &out_d,
-                           &flags, &counters, &spill, &stats, &ranges, &qs, &ns, &inv, &res, &res_w, &resume, &p2cand};
+                           &flags, &counters, &spill, &stats, &ranges, &qs, &ns, &inv, &res, &res_w, &resume, &p2cand, &sgn};
     size_t t = 0;
     for (const DevBuf* b : all) t += b->bytes;
     return t;
@@ -432,6 +432,7 @@ static void free_tree(msh_tree* t) {
     if (t->d_vorder_shard) (void)dfree(t->d_vorder_shard);
     if (t->d_cut) (void)dfree(t->d_cut);
     if (t->d_face_leaf) (void)dfree(t->d_face_leaf);
+    if (t->d_sign) (void)dfree(t->d_sign);
     for (int b = 0; b < 3; ++b) {
         if (b < 2 && t->h_stage[b]) (void)hipHostFree(t->h_stage[b]);
         if (t->d_stage[b]) (void)dfree(t->d_stage[b]);
@@ -1983,6 +1984,186 @@ int msh_tree_nearest_stats(msh_tree* t, const double* d_q, size_t S, uint64_t* n
         fprintf(stderr, "[msh leaves] improving_phase_tests=%llu hinted=%llu hint_leaf_won=%llu\n", h[36], h[37], h[38]);
     }
     return MSH_OK;
+}
+
+// ---- signed distance (sign.hip) ----
+// plain triangle trees only: the table's faces are the tree's leaves, one to one
+static int check_sign_tree(const msh_tree* t, const char* fn) {
+    MSH_TRY(check_tree(t, kTriangles, fn));
+    if (t->kind != kTriangles) {
+        set_error("%s: normals-metric tree handle (signed distance needs a plain triangle tree)", fn);
+        return MSH_EINVAL;
+    }
+    if (t->T != t->T_main) {
+        set_error("%s: the tree was built with extra faces (%zu of %zu leaves are the main mesh's)", fn, t->T_main, t->T);
+        return MSH_EINVAL;
+    }
+    return MSH_OK;
+}
+
+static int check_sign_built(const msh_tree* t, const char* fn) {
+    if (!t->d_sign) {
+        set_error("%s: the tree has no sign table (call msh_tree_sign_build first)", fn);
+        return MSH_EINVAL;
+    }
+    return MSH_OK;
+}
+
+static void free_sign_table(msh_tree* t) {
+    if (t->d_sign) {
+        (void)hipSetDevice(t->device);
+        if (t->ws_done) (void)hipEventSynchronize(t->ws_done);  // no launch may still read the table
+        (void)dfree(t->d_sign);
+    }
+    t->d_sign = nullptr;
+    t->sign = msh_sign_info{0, 0, 0, 0, 0, 0, 0.0};
+}
+
+// the table of one handle (its own device and stream; scratch of its own, released on return)
+static int sign_build_one(msh_tree* t, const uint32_t* f) {
+    MSH_TRY(use_device(t->device));
+    hipStream_t s = t->stream;
+    const size_t bytes = sign_table_bytes(t->P, t->T);
+    void* block = nullptr;
+    MSH_HIP(dmalloc(&block, bytes));
+    Workspace ws;
+    DevBuf dF;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    uint32_t h[5] = {0, 0, 0, 0, 0};
+    float ms = 0.f;
+    int st = MSH_OK;
+    do {
+        hipError_t e = hipEventCreate(&e0);
+        if (e == hipSuccess) e = hipEventCreate(&e1);
+        if (e != hipSuccess) { set_error("msh_tree_sign_build: %s", hipGetErrorString(e)); st = MSH_EDEVICE; break; }
+        if ((st = upload(dF, f, 3 * t->T, s)) != MSH_OK) break;
+        if ((st = ws.counters.reserve(sizeof(h))) != MSH_OK) break;
+        e = hipMemsetAsync(ws.counters.ptr, 0, sizeof(h), s);
+        if (e == hipSuccess) e = hipEventRecord(e0, s);
+        if (e != hipSuccess) { set_error("msh_tree_sign_build: %s", hipGetErrorString(e)); st = MSH_EDEVICE; break; }
+        if ((st = sign_table_build(t, dF.as<uint32_t>(), block, ws.counters.as<uint32_t>(), ws, s)) != MSH_OK) break;
+        e = hipEventRecord(e1, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(h, ws.counters.ptr, sizeof(h), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { set_error("msh_tree_sign_build: %s", hipGetErrorString(e)); st = MSH_EDEVICE; break; }
+        (void)hipEventElapsedTime(&ms, e0, e1);
+    } while (0);
+    (void)hipStreamSynchronize(s);  // the scratch below is released on return
+    ws.release();
+    dF.release();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (st == MSH_OK && (h[4] & 1u)) {
+        set_error("msh_tree_sign_build: face index out of range (>= %zu vertices)", t->P);
+        st = MSH_EINVAL;
+    }
+    if (st == MSH_OK && (h[4] & 2u)) {
+        set_error("msh_tree_sign_build: faces do not match the tree (a leaf's corners differ from v[f[face]])");
+        st = MSH_EINVAL;
+    }
+    if (st != MSH_OK) {
+        (void)dfree(block);
+        return st;
+    }
+    free_sign_table(t);
+    t->d_sign = block;
+    t->sign = msh_sign_info{1, h[0], h[1], h[2], h[3], bytes, ms};
+    return MSH_OK;
+}
+
+int msh_tree_sign_build(msh_tree* t, const uint32_t* f, size_t T) {
+    MSH_TRY(check_sign_tree(t, "msh_tree_sign_build"));
+    if (!f) { set_error("msh_tree_sign_build: null faces"); return MSH_EINVAL; }
+    if (T != t->T) {
+        set_error("msh_tree_sign_build: %zu faces given, the tree holds %zu", T, t->T);
+        return MSH_EINVAL;
+    }
+    int st = sign_build_one(t, f);
+    for (size_t g = 0; g < t->replicas.size() && st == MSH_OK; ++g) st = sign_build_one(t->replicas[g], f);
+    if (st != MSH_OK) {  // all or none: the host entry point splits its rows over every replica
+        const std::string keep = g_err;
+        free_sign_table(t);
+        for (msh_tree* r : t->replicas) free_sign_table(r);
+        g_err = keep;
+    }
+    (void)use_device(t->device);
+    return st;
+}
+
+int msh_tree_sign_info(const msh_tree* t, msh_sign_info* info) {
+    if (!t || !info) { set_error("msh_tree_sign_info: null argument"); return MSH_EINVAL; }
+    *info = t->sign;
+    return MSH_OK;
+}
+
+// the closest-point launch of nearest_run, then the sign pass over its answers in caller order (part codes from
+// workspace scratch when the caller wants none)
+static int signed_run(msh_tree* t, const double* d_q, size_t S, double* d_sdist, uint32_t* d_face, uint32_t* d_part,
+                      double* d_pt, hipStream_t s) {
+    WsOrder order(t, s);
+    if (!d_part) {
+        MSH_TRY(t->ws.sgn.reserve(S * sizeof(uint32_t)));
+        d_part = t->ws.sgn.as<uint32_t>();
+    }
+    QueryOrder ord;
+    MSH_TRY(sort_queries(t, d_q, nullptr, S, s, &ord, true));
+    MSH_TRY(launch_nearest(t, ord, S, SlotOut{d_face, d_part, d_pt, nullptr, nullptr}, s));
+    return launch_sign_pass(sign_table_of(t->d_sign, t->P, t->T), t->T, t->P, d_q, S, d_face, d_part, d_pt, d_sdist, s);
+}
+
+int msh_tree_signed_distance_device(msh_tree* t, const double* d_q, size_t S, double* d_sdist, uint32_t* d_face,
+                                    uint32_t* d_part, double* d_pt, void* stream) {
+    MSH_TRY(check_sign_tree(t, "msh_tree_signed_distance_device"));
+    MSH_TRY(check_count(S, "msh_tree_signed_distance_device"));
+    MSH_TRY(check_sign_built(t, "msh_tree_signed_distance_device"));
+    if (S == 0) return MSH_OK;
+    if (!d_q || !d_sdist || !d_face || !d_pt) {
+        set_error("msh_tree_signed_distance_device: null argument");
+        return MSH_EINVAL;
+    }
+    ensure_entry_cut(t, S);
+    return signed_run(t, d_q, S, d_sdist, d_face, d_part, d_pt, pick(t, stream));
+}
+
+int msh_tree_sign_from_faces_device(msh_tree* t, const double* d_q, size_t S, const uint32_t* d_face,
+                                    const uint32_t* d_part, const double* d_pt, double* d_sdist, void* stream) {
+    MSH_TRY(check_sign_tree(t, "msh_tree_sign_from_faces_device"));
+    MSH_TRY(check_count(S, "msh_tree_sign_from_faces_device"));
+    MSH_TRY(check_sign_built(t, "msh_tree_sign_from_faces_device"));
+    if (S == 0) return MSH_OK;
+    if (!d_q || !d_face || !d_part || !d_pt || !d_sdist) {
+        set_error("msh_tree_sign_from_faces_device: null argument");
+        return MSH_EINVAL;
+    }
+    // no workspace is used (the table only), so no WsOrder, as msh_tree_points_from_faces_device
+    return launch_sign_pass(sign_table_of(t->d_sign, t->P, t->T), t->T, t->P, d_q, S, d_face, d_part, d_pt, d_sdist,
+                            pick(t, stream));
+}
+
+int msh_tree_signed_distance(msh_tree* t, const double* q, size_t S, double* sdist, uint32_t* face, uint32_t* part,
+                             double* pt) {
+    MSH_TRY(check_sign_tree(t, "msh_tree_signed_distance"));
+    MSH_TRY(check_count(S, "msh_tree_signed_distance"));
+    MSH_TRY(check_sign_built(t, "msh_tree_signed_distance"));
+    for (const msh_tree* r : t->replicas) MSH_TRY(check_sign_built(r, "msh_tree_signed_distance"));
+    if (S == 0) return MSH_OK;
+    if (!q || !sdist || !face || !pt) { set_error("msh_tree_signed_distance: null argument"); return MSH_EINVAL; }
+    return fan_out(t, S, 64, [&](msh_tree* h, size_t r0, size_t S_h) {
+        MSH_TRY(use_device(h->device));
+        ensure_entry_cut(h, S);
+        // rows: q (24 B in) | sdist (8 B out) | face (4 B out) | part (4 B out) | point (24 B out); the part slab
+        // serves the sign pass also when the caller wants no parts
+        const std::vector<HostArr> arrs = {{q + 3 * r0, nullptr, 24},
+                                           {nullptr, sdist + r0, 8},
+                                           {nullptr, face + r0, 4},
+                                           {nullptr, part ? part + r0 : nullptr, 4},
+                                           {nullptr, pt + 3 * r0, 24}};
+        return pipelined(h, S_h, arrs, [&](size_t, size_t n, const std::vector<char*>& d) {
+            return signed_run(h, reinterpret_cast<const double*>(d[0]), n, reinterpret_cast<double*>(d[1]),
+                              reinterpret_cast<uint32_t*>(d[2]), reinterpret_cast<uint32_t*>(d[3]),
+                              reinterpret_cast<double*>(d[4]), h->stream);
+        });
+    });
 }
 
 // the rays' walks start from the tree's entry cut (built by the automatic policy on these rows too: rays_cut)

@@ -74,7 +74,7 @@ struct DevBuf {
 // results / staging).
 struct Workspace {
     DevBuf keys, vals, keys_alt, vals_alt, hist, scan, q, n, out_a, out_b, out_c, out_d, flags, counters, spill, stats,
-        ranges, qs, ns, inv, res, res_w, resume, p2cand;
+        ranges, qs, ns, inv, res, res_w, resume, p2cand, sgn;
     void release();
     size_t bytes() const;
 };
@@ -157,6 +157,10 @@ struct msh_tree {
     uint32_t* d_cut = nullptr;
     int cut_wide = 0;
     uint32_t* d_face_leaf = nullptr;  // face -> leaf (msh_tree_points_from_faces_device; built on first use)
+    // sign table (msh_tree_sign_build; sign.hip): one device block holding fn (T,3) f64, vpn (P,3) f64, opp (T,3) u32
+    // and f (T,3) u32 in that order; nullptr until built (blobs leave it out)
+    void* d_sign = nullptr;
+    msh_sign_info sign = {0, 0, 0, 0, 0, 0, 0.0};
     int cut_G = 0;
     // lazily built on the first closest-point query (msh_tree_set_entry_cut): requested grid (< 0 automatic,
     // 0 off), state (0 pending, 1 built, 2 off / not applicable, 3 failed), GPU build time
@@ -306,6 +310,33 @@ int launch_tri_intersect(const msh_tree* tree, const TriRec* d_qtris, size_t Tq,
 // d_err (device u32, zeroed by the caller) is set when a face index is >= P (those faces are ignored)
 int vertex_normals(const double* d_v, size_t P, const uint32_t* d_f, size_t T, double* d_vn, Workspace& ws,
                    hipStream_t s, uint32_t* d_err);
+
+// ---- signed distance (sign.hip) ----
+// The sign table of a triangle tree: unit face normals, the face across each edge (k = 0/1/2 for ab/bc/ca, the part
+// codes 1/2/3), the face array and the angle-weighted vertex pseudonormals (Baerentzen and Aanaes 2005).
+struct SignTable {
+    const double* fn;     // (T,3) unit face normals (zero for a zero-area face)
+    const double* vpn;    // (P,3) sum over incident faces of (angle at the vertex) x (unit face normal)
+    const uint32_t* opp;  // (T,3) face across edge k, MSH_NO_FACE on a boundary or non-manifold edge
+    const uint32_t* f;    // (T,3)
+};
+inline size_t sign_table_bytes(size_t P, size_t T) { return 48 * T + 24 * P; }
+// the sections of a block of sign_table_bytes(P, T) bytes (256-B aligned base)
+inline SignTable sign_table_of(void* block, size_t P, size_t T) {
+    char* b = static_cast<char*>(block);
+    return SignTable{reinterpret_cast<const double*>(b), reinterpret_cast<const double*>(b + 24 * T),
+                     reinterpret_cast<const uint32_t*>(b + 24 * T + 24 * P),
+                     reinterpret_cast<const uint32_t*>(b + 24 * T + 24 * P + 12 * T)};
+}
+// Fills `block` from the faces d_f (T,3) on the device, checked against the tree's leaves and vertices.
+// d_counts (5 u32, zeroed by the caller): boundary, non-manifold and inconsistent edges, degenerate faces, and an error
+// word (bit 0: a face index >= P, bit 1: a leaf's corners differ from v[f[face]]).  Asynchronous on s.
+int sign_table_build(const msh_tree* tree, const uint32_t* d_f, void* block, uint32_t* d_counts, Workspace& ws,
+                     hipStream_t s);
+// sdist[i] = +-|q[i] - pt[i]|, negative where (q - pt) . N < 0 for the pseudonormal N of (face[i], part[i]);
+// NaN for face >= T
+int launch_sign_pass(const SignTable& tab, size_t T, size_t P, const double* d_q, size_t S, const uint32_t* d_face,
+                     const uint32_t* d_part, const double* d_pt, double* d_sdist, hipStream_t s);
 
 // ---- timing ----
 struct TimedLaunch {

@@ -286,6 +286,23 @@ def _stream(t, stream):
     return torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
 
 
+def signed_distance_device(tree, q, sdist, face, part, pt, stream=None):
+    """Device-resident signed distance (msh_tree_signed_distance_device) on torch tensors: q (S,3) f64, sdist (S,)
+    f64, face / part (S,) int32 viewed as uint32, pt (S,3) f64; part may be None.  The tree needs its sign table
+    (tree.sign_build()).  Asynchronous on `stream` (default: torch's current stream)."""
+    _native.check(_native.lib().msh_tree_signed_distance_device(
+        tree.ptr, q.data_ptr(), q.shape[0], sdist.data_ptr(), face.data_ptr(),
+        part.data_ptr() if part is not None else None, pt.data_ptr(), _stream(q, stream)))
+
+
+def sign_from_faces_device(tree, q, face, part, pt, sdist, stream=None):
+    """The sign pass alone (msh_tree_sign_from_faces_device): sdist (S,) f64 for given (face, part, point) rows, e.g.
+    the rows NarrowRing rebuilt with points_from_faces_device.  Asynchronous on `stream`."""
+    _native.check(_native.lib().msh_tree_sign_from_faces_device(
+        tree.ptr, q.data_ptr(), q.shape[0], face.data_ptr(), part.data_ptr(), pt.data_ptr(), sdist.data_ptr(),
+        _stream(q, stream)))
+
+
 def nearest_bary_device(tree, q, face, pt, w, stream=None):
     """Device-resident closest point + barycentric weights (msh_tree_nearest_bary_device): q (S,3) f64,
     face (S,) int32 viewed as uint32, pt (S,3) f64, w (S,3) f64."""

@@ -60,6 +60,39 @@ class AabbTree(object):
         from . import spatialsearch
         return spatialsearch.aabbtree_nearest_barycentric(self.cpp_handle, _f64c(v_samples))
 
+    def orientation_info(self):
+        """Topology counters of the mesh as the sign table sees it (built on first use): a dict with
+        ``boundary_edges``, ``nonmanifold_edges``, ``inconsistent_edges`` and ``degenerate_faces``.  All zero:
+        the mesh is a closed, consistently oriented manifold and ``signed_distance`` is exact."""
+        h = self.cpp_handle
+        info = h.sign_info()
+        if info["state"] != "built":
+            info = h.sign_build()
+        return dict((k, info[k]) for k in ("boundary_edges", "nonmanifold_edges", "inconsistent_edges",
+                                           "degenerate_faces"))
+
+    def signed_distance(self, v_samples, check=True):
+        """(sdist (S,) f64, face (S,) u32, point (S,3) f64): the closest face and point of ``nearest`` and the
+        signed distance to it, negative inside an outward-oriented mesh (angle-weighted pseudonormal test).
+
+        With ``check=True`` a mesh that is not a closed, consistently oriented manifold raises ValueError naming
+        the counts of ``orientation_info``.  With ``check=False`` the query runs anyway: a boundary or non-manifold
+        edge uses its own face's normal, an inconsistent edge the sum of both, a degenerate face a zero normal,
+        and the sign is undefined near those features."""
+        from . import spatialsearch
+        if check:
+            bad = dict((k, n) for k, n in self.orientation_info().items() if n)
+            if bad:
+                raise ValueError("mesh is not a closed, consistently oriented manifold: %s" %
+                                 ", ".join("%d %s" % (n, k.replace("_", " ")) for k, n in sorted(bad.items())))
+        sdist, face, _, pt = spatialsearch.aabbtree_signed_distance(self.cpp_handle, _f64c(v_samples))
+        return sdist, face, pt
+
+    def contains(self, v_samples, check=True):
+        """bool (S,): whether each sample lies inside the mesh (``signed_distance < 0``; points on the surface
+        and non-finite rows are not inside)."""
+        return self.signed_distance(v_samples, check)[0] < 0
+
     def intersections_indices(self, q_v, q_f):
         """Indices (ascending, u32) of the query triangles ``q_v[q_f]`` that touch the mesh.
 

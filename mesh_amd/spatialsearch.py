@@ -60,6 +60,37 @@ def aabbtree_nearest(tree, q):
     return face, part, pt
 
 
+def aabbtree_signed_distance(tree, q):
+    """(sdist (S,) float64, face (S,) uint32, part (S,) uint32, point (S,3) float64): ``aabbtree_nearest``'s answer
+    and the signed distance to it -- negative inside an outward-oriented closed mesh, positive outside, NaN on
+    non-finite rows (no reference counterpart).
+
+    The sign is that of ``(q - point) . N`` with N the angle-weighted pseudonormal of the feature the closest point
+    lies on (chosen by ``part``; Baerentzen and Aanaes 2005): exact on a closed, consistently oriented manifold mesh,
+    undefined near the edges and faces ``tree.sign_info()`` counts otherwise.  The table behind it is built on
+    first use from ``tree.faces``; a handle that keeps no faces (one unpacked from a blob) needs
+    ``tree.sign_build(f)`` first."""
+    tree = _tree(tree, "aabbtree_signed_distance")
+    if not isinstance(q, np.ndarray):
+        raise TypeError("aabbtree_signed_distance() argument 2 must be numpy.ndarray")
+    if q.ndim != 2 or q.shape[1] != 3:
+        raise ValueError("Input must be Nx3")
+    if tree.kind != "triangles":
+        raise TypeError("aabbtree_signed_distance: handle is not a triangle tree")
+    q = np.ascontiguousarray(q, dtype=np.float64)
+    if tree.sign_info()["state"] != "built":
+        if tree.faces is None:
+            raise ValueError("aabbtree_signed_distance: the tree has no sign table and keeps no face array: "
+                             "call tree.sign_build(f) with the faces it was built with")
+        tree.sign_build()
+    S = q.shape[0]
+    sdist, face, part, pt = N.empty_results(((S,), np.float64), ((S,), np.uint32), ((S,), np.uint32),
+                                            ((S, 3), np.float64))
+    N.check(N.lib().msh_tree_signed_distance(tree.ptr, N.dptr(q), S, N.dptr(sdist), N.uptr(face), N.uptr(part),
+                                             N.dptr(pt)))
+    return sdist, face, part, pt
+
+
 def aabbtree_nearest_barycentric(tree, q):
     """(face (S,) uint32, point (S,3) float64, weights (S,3) float64) of the closest point.
 
