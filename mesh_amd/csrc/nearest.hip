@@ -376,13 +376,19 @@ struct WalkerT {
     // since the stack entry it would get is the one the following pop returns.
     // PF: the node was prefetched into this lane's LDS slot (nb; node_prefetch), and the next one is prefetched
     // before returning
+    // The query's best leaf is never handed back: pol.best_leaf is only ever set from an exact evaluation of that leaf
+    // for this query (the hint test, a round's merge, a deferral record), so a second one could only offer the
+    // (d2, face) the query already holds, a duplicate in a lexicographic minimum.  With no best yet (-1) the ref
+    // compared against is 0, which no leaf ref (negative) equals.  A node whose two leaf children include it queues
+    // the other and parks nothing.
     template <class Pol, bool STATS, bool PF = false>
     __device__ inline bool step_collect(const BNode* __restrict__ nodes, const QF& qf, const Pol& pol,
                                         Ent* __restrict__ lds, uint2* __restrict__ spill, unsigned& n_nodes, int& p0,
                                         int& p1, int room = 2, const float4* nb = nullptr, uint32_t wsl = 0) {
         bool more = false;  // `node` holds the next entry; otherwise pop
+        const int seen = ~pol.best_leaf;  // the best leaf's ref: already evaluated for this query (0 while there is none)
         if (node < 0) {
-            p0 = ~node;
+            if (node != seen) p0 = ~node;
         } else {
             const NodeV nd = PF ? node_from_lds(nb) : load_node(nodes, node);
             if (STATS) ++n_nodes;
@@ -391,7 +397,8 @@ struct WalkerT {
             const int c0 = nd.child(0), c1 = nd.child(1);
             const float lim = pol.limf;
             const bool h0 = d0 <= lim, h1 = d1 <= lim;
-            const bool l0 = h0 && c0 < 0, l1 = h1 && c1 < 0;  // leaf children within the bound
+            // leaf children within the bound, but for the best leaf
+            const bool l0 = h0 && c0 < 0 && c0 != seen, l1 = h1 && c1 < 0 && c1 != seen;
             const bool i0 = h0 && c0 >= 0, i1 = h1 && c1 >= 0;  // internal children within the bound
             const bool first1 = d1 < d0;                         // child 1 is the nearer
             if (l0 && l1) {
@@ -422,13 +429,19 @@ struct WalkerT {
     // cut records hold ~leaf refs).  One wave-uniform test covers the deep stack: when no lane of the step holds
     // kStack entries or more, the push writes LDS (index sp < kStack) and every pop reads it (indices < sp <= kStack),
     // so the common step carries no spill branch; spill_of() yields this lane's global spill column, only when needed.
+    // `seen` is the cell's hint leaf (-1: none), which the kernel evaluates before the walk: a leaf child equal to it is
+    // not handed back, since a second construction could only offer the (d2, face) already offered.  Here that covers
+    // step_collect's best-leaf rule and more: every other leaf is evaluated after the walk hands it back, and the walk
+    // enters a node once, so the best leaf can be reached again only while it is still the hint -- and the hint is
+    // dropped also after a better leaf replaced it.  Two compares per step; a ~leaf cut entry equal to the hint is
+    // dropped once, by cut_start_narrow.
     template <class Pol, class SpillOf>
     __device__ inline bool step_list(const BNode* __restrict__ nodes, const QF& qf, const Pol& pol, Ent* __restrict__ lds,
-                                     SpillOf&& spill_of, int& p0, int& p1, const float4* nb, uint32_t wsl) {
+                                     SpillOf&& spill_of, int& p0, int& p1, const float4* nb, uint32_t wsl, int seen) {
         const bool deep = __ballot(sp >= kStack) != 0ull;
         bool more = false;
         if (node < 0) {
-            p0 = ~node;
+            p0 = ~node;  // a cut entry (nothing parks a leaf here), and never the hint leaf: cut_start_narrow
         } else {
             const NodeV nd = node_from_lds(nb);
             float d0, d1;
@@ -436,11 +449,12 @@ struct WalkerT {
             const int c0 = nd.child(0), c1 = nd.child(1);
             const float lim = pol.limf;
             const bool h0 = d0 <= lim, h1 = d1 <= lim;
-            const bool l0 = h0 && c0 < 0, l1 = h1 && c1 < 0;
+            const int f0 = ~c0, f1 = ~c1;
+            const bool l0 = h0 && c0 < 0 && f0 != seen, l1 = h1 && c1 < 0 && f1 != seen;
             const bool i0 = h0 && c0 >= 0, i1 = h1 && c1 >= 0;
             const bool first1 = d1 < d0;
-            if (l0) p0 = ~c0;
-            if (l1) p1 = ~c1;
+            if (l0) p0 = f0;
+            if (l1) p1 = f1;
             if (i0 && i1) {
                 const Ent e = E::make((unsigned)(first1 ? c0 : c1), __float_as_uint(first1 ? d0 : d1));
                 if (!deep)
@@ -782,9 +796,13 @@ __device__ inline bool cut_start_narrow(const uint32_t* __restrict__ cut, size_t
     const uint4* c = reinterpret_cast<const uint4*>(cut + cell * 8);
     const uint4 e0 = c[0], e1 = c[1];
     const uint32_t e[kCutK] = {e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
+    // the cell's hint leaf, evaluated before the walk (pol.best_leaf), is not entered again as a ~leaf entry: whatever
+    // the best is when its turn comes, its construction could not change it.  Without a hint nothing matches: entries
+    // are node refs too (0 is the root), and INT_MIN is no 21-bit ref
+    const int seen = pol.best_leaf >= 0 ? ~pol.best_leaf : INT_MIN;
 #pragma unroll
     for (int j = kCutK - 1; j >= 0; --j)
-        if ((int)e[j] >= 0) {
+        if ((int)e[j] >= 0 && Ent4::ref(e[j]) != seen) {
             lds[w.sp * kBlock] = Ent4::make((uint32_t)Ent4::ref(e[j]), e[j] & 0xFFE00000u);
             ++w.sp;
         }
@@ -1274,7 +1292,8 @@ __global__ __launch_bounds__(kBlock) MSH_KNN_ATTR void k_knn(KnnArgs a) {
 // path with the node prefetch, written out without the leader / follower starts, the T == 1 path, wide cut records,
 // slot-order records, the inv_w store and the instrumented counters.  Its cold arguments are read from the kernarg
 // segment after the tile's wave loop (cold_arg), its node step keeps two ring places free and puts the deep stack
-// behind one wave-uniform test (WalkerT::step_list), and a lane's walk state is one register.  Against k_knn: 80 SGPR
+// behind one wave-uniform test (WalkerT::step_list), and a lane's walk state is one register.  The walk does not queue
+// the cell's hint leaf, evaluated before it starts, a second time (step_list; profiles/r10_*).  Against k_knn: 80 SGPR
 // spills -> 3, none in the loop; C3 100M 2.533-2.557 -> 2.592-2.610 G q/s (profiles/r07_knn_lean_isa.txt,
 // r07_c3_knn_lean_ab.jsonl).  The ring code (run_rounds, the append) is k_knn's, statement for statement.
 template <int MODE>
@@ -1323,6 +1342,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MSH_KNN_
             const int lf = cut_hint_leaf(a.cut[cell * 8]);
             if (lf >= 0) pol.test(lf);
         }
+        const int hint = pol.best_leaf;  // evaluated: the walk does not queue it again (step_list; -1: none)
         QF qf;
         const double o[3] = {a.org[0], a.org[1], a.org[2]};  // single tree
         qf = make_qf(q, o, a.tm);
@@ -1394,7 +1414,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MSH_KNN_
             if (!any && tail == head) break;  // nothing queued and nobody can move: the tile is done
             int l0 = -1, l1 = -1;
             if (can) {
-                active = w.step_list(a.nodes, qf, pol, lds, spill_col, l0, l1, nb, wsl);
+                active = w.step_list(a.nodes, qf, pol, lds, spill_col, l0, l1, nb, wsl, hint);
                 ++steps;
                 if (active && steps >= max_steps) active = false;  // each node is entered once: corrupt tree
                 st = !active ? kIdle : (steps == budget ? kPast : kWalk);
