@@ -528,14 +528,6 @@ static void free_entry_cut(msh_tree* t) {
 #ifndef MSH_CUT_MAX_LOG2
 #define MSH_CUT_MAX_LOG2 26
 #endif
-#ifndef MSH_CUT_FROM_HALF
-#define MSH_CUT_FROM_HALF 1
-#endif
-constexpr bool kCutFromHalf = MSH_CUT_FROM_HALF;
-#ifndef MSH_CUT_STAGED
-#define MSH_CUT_STAGED 1
-#endif
-constexpr bool kCutStaged = MSH_CUT_STAGED;
 constexpr size_t kCutCoarsePerLeaf = 8;
 constexpr int kCutCoarseMaxLog2 = 23;
 constexpr size_t kFineRowsPerCell = 16;
@@ -551,8 +543,7 @@ static size_t cut_rec_bytes(const msh_tree* t) { return t->T <= kEnt4MaxLeaves ?
 static int cut_grid(const msh_tree* t, bool fine) {
     if (t->cut_req > 0) return t->cut_req;
     const int Gc = std::max(16, (int)std::lround(std::cbrt((double)auto_cut_cells(t, false))));
-    if (!fine) return Gc;
-    return kCutFromHalf ? 2 * Gc : std::max(16, (int)std::lround(std::cbrt((double)auto_cut_cells(t, true))));
+    return fine ? 2 * Gc : Gc;
 }
 
 // The grid's cell centres are answered exactly by the tree (walks from the installed coarse grid when the fine one is
@@ -636,7 +627,7 @@ static int build_entry_cut(msh_tree* t, bool fine) {
             // the installed grid, when it is this one at half resolution over the same box (the automatic coarse grid
             // under the fine one), gives every cell its start list (k_cut_level)
             const uint32_t* half = nullptr;
-            if (kCutFromHalf && t->d_cut && 2 * t->cut_G == G && t->cut_wide == (e4 ? 0 : 1) &&
+            if (t->d_cut && 2 * t->cut_G == G && t->cut_wide == (e4 ? 0 : 1) &&
                 t->cut_lo[0] == lo[0] && t->cut_lo[1] == lo[1] && t->cut_lo[2] == lo[2])
                 half = t->d_cut;
             if ((st = cut_level(t, G, lo, w, dp.as<double>(), dhint.as<int>(), cut, e4, s, half,
@@ -706,7 +697,7 @@ static void ensure_entry_cut(msh_tree* t, size_t S) {
     // two stages: the coarse grid first (its own centre walks from the root), then the fine one, whose centre walks and
     // start lists begin from it (build_entry_cut); the coarse grid is then freed like an upgrade's
     double staged_ms = 0.0;
-    if (kCutStaged && fine && !t->d_cut && t->cut_req < 0) {
+    if (fine && !t->d_cut && t->cut_req < 0) {
         t->cut_state = kCutOff;
         if (build_entry_cut(t, false) == MSH_OK) {
             staged_ms = t->cut_ms;
@@ -811,14 +802,10 @@ static int build_triangles(msh_tree* t, const double* v, size_t Pall, const uint
 }
 
 static const size_t kSortMin = 4096;  // below this the query Morton sort costs more than it saves
-#ifndef MSH_ALONG_LAZY
-#define MSH_ALONG_LAZY 1
-#endif
-static constexpr bool kAlongLazy = MSH_ALONG_LAZY;  // alongnormal rays read at perm[slot] instead of gathered
 
 // Query order for S point rows (device): below kSortMin the caller's arrays are used as they are;
 // otherwise Morton codes + radix sort give the permutation (ws.vals).  With allow_lazy (closest-point
-// launches, and alongnormal rays with their normals: kAlongLazy) the traversal reads row perm[i] itself (and the
+// launches, and alongnormal rays with their normals) the traversal reads row perm[i] itself (and the
 // closest-point one writes the inverse permutation, ws.inv); otherwise (the normals-metric queries) the rows and
 // normals are gathered once into slot order (ws.qs / ws.ns) with the inverse permutation (gathering the
 // closest-point rows too measured 3 % slower on C3; the C5 rays 0.5 ms slower, profiles/r06_c5_along_lazy_ab.jsonl).
@@ -2171,7 +2158,7 @@ static int along_run(msh_tree* t, const double* d_p, const double* d_n, size_t S
                      double* d_pt, hipStream_t s) {
     WsOrder order(t, s);
     QueryOrder ord;
-    MSH_TRY(sort_queries(t, d_p, d_n, S, s, &ord, kAlongLazy));
+    MSH_TRY(sort_queries(t, d_p, d_n, S, s, &ord, true));
     return launch_alongnormal(t, ord, S, SlotOut{d_face, nullptr, d_pt, nullptr, d_dist}, s);
 }
 
@@ -2205,7 +2192,7 @@ int msh_tree_nearest_alongnormal_stats(msh_tree* t, const double* d_p, const dou
     {
         WsOrder order(t, s);
         QueryOrder ord;
-        MSH_TRY(sort_queries(t, d_p, d_n, S, s, &ord, kAlongLazy));
+        MSH_TRY(sort_queries(t, d_p, d_n, S, s, &ord, true));
         MSH_TRY(t->ws.stats.reserve(8 * sizeof(unsigned long long)));
         MSH_HIP(hipMemsetAsync(t->ws.stats.ptr, 0, 8 * sizeof(unsigned long long), s));
         MSH_TRY(launch_alongnormal_stats(t, ord, S, t->ws.stats.as<unsigned long long>(), s));

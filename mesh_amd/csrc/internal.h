@@ -252,10 +252,6 @@ constexpr size_t kEnt4MaxLeaves = (size_t)1 << 20;  // 4-B stack / cut entries: 
 // k_cut_level's directional drop (nearest.hip cut_dir_drop) and the mark of a record it shortened: bit 30 of word 0
 // (the hint leaf; leaves < 2^26) in 32-B records -- 64-B records zero their radius word instead.  The alongnormal
 // walks start at the root in a marked cell (rays.hip); the closest-point walks mask the bit.
-#ifndef MSH_CUT_DIRECTIONAL
-#define MSH_CUT_DIRECTIONAL 1
-#endif
-constexpr bool kCutDirectional = MSH_CUT_DIRECTIONAL != 0;
 constexpr uint32_t kCutDirFlag = 0x40000000u;
 int cut_centres(int G, const double* lo, const double* w, double* d_q, hipStream_t s);
 // d_half: the records of the G/2 grid over the same box (same record size), each cell then starts from its enclosing

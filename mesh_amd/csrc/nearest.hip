@@ -2481,7 +2481,7 @@ int cut_level(const msh_tree* tree, int G, const double* lo, const double* w, co
         kern<<<nb, kBlock, 0, s>>>(tree->d_nodes, tris, tree->origin[0], tree->origin[1], tree->origin[2], tm, G, lo[0], lo[1],
                                    lo[2], w[0], w[1], w[2], d_pts, d_hint, d_rec, d_half, d_nflag);
     };
-    if (directional && kCutDirectional)
+    if (directional)
         e4 ? launch(k_cut_level<true, true>) : launch(k_cut_level<false, true>);
     else
         e4 ? launch(k_cut_level<true, false>) : launch(k_cut_level<false, false>);

@@ -92,20 +92,17 @@ __device__ inline bool cgal_plane_line(const D3& p, const D3& d, const D3& a, co
 __device__ inline D3 ray_dir(const D3& p, const D3& v) { return vsub(vadd(p, v), p); }
 
 // ---- generic traversal: the policy decides box hits (and ordering key) and leaf tests ----
-// PF: each next node is loaded into the lane's LDS slot (nb; node_prefetch) as soon as it is chosen; D: LDS stack depth
-template <class Pol, bool STATS, bool PF = false, int D = kStack>
+template <class Pol, bool STATS>
 __device__ inline void traverse_rays(const BNode* __restrict__ nodes, size_t T, Pol& pol, uint2* __restrict__ lds,
-                                     uint2* __restrict__ spill, unsigned& n_nodes, unsigned& n_leaves,
-                                     const float4* nb = nullptr, uint32_t wsl = 0) {
+                                     uint2* __restrict__ spill, unsigned& n_nodes, unsigned& n_leaves) {
     if (T == 1) {
         pol.test(0);
         if (STATS) ++n_leaves;
         return;
     }
     int node = 0, sp = 0;
-    if (PF) node_prefetch(nodes, 0, wsl);
     for (size_t guard = 0; guard < T; ++guard) {
-        const NodeV nd = PF ? node_from_lds(nb) : load_node(nodes, node);
+        const NodeV nd = load_node(nodes, node);
         if (STATS) ++n_nodes;
         bool h0, h1;
         float k0, k1;
@@ -130,21 +127,19 @@ __device__ inline void traverse_rays(const BNode* __restrict__ nodes, size_t T, 
             float kf = k1;
             if (k1 < k0) { nearc = c1; farc = c0; kf = k0; }
             const uint2 e = make_uint2((unsigned)farc, __float_as_uint(kf));
-            stack_put<D>(lds, spill, sp, e);
+            stack_put(lds, spill, sp, e);
             ++sp;
             node = nearc;
-            if (PF) node_prefetch(nodes, node, wsl);
             continue;
         }
         if (h0 || h1) {
             node = h0 ? c0 : c1;
-            if (PF) node_prefetch(nodes, node, wsl);
             continue;
         }
         bool found = false;
         while (sp > 0) {
             --sp;
-            const uint2 e = stack_get<D>(lds, spill, sp);
+            const uint2 e = stack_get(lds, spill, sp);
             if (pol.keep(__uint_as_float(e.y))) {
                 node = (int)e.x;
                 found = true;
@@ -152,7 +147,6 @@ __device__ inline void traverse_rays(const BNode* __restrict__ nodes, size_t T, 
             }
         }
         if (!found) break;
-        if (PF) node_prefetch(nodes, node, wsl);
     }
 }
 
@@ -224,174 +218,6 @@ struct AlongPol {
     }
 };
 
-// nearest_alongnormal with the wave leaf list (K2's scheme, nearest.hip k_knn): a lane appends the leaf children that
-// pass its node test to a ring of (leaf << 6 | owner lane) entries in LDS shared by the wave and keeps walking (until
-// kAlongPend of its leaves wait); whenever 64 entries wait the wave tests them in a full round, one entry per lane --
-// the owner's (p, n) by ds_bpermute, both directions through one copy of the fp64 code -- and the results go back
-// through LDS: an atomic min of the distance's bits per owner, then among the entries that reached it an atomic min
-// of (face << 32 | leaf): the lexicographic (distance, face) rule of AlongPol::test.  Per-lane leaf tests ran with
-// 31 % of the lanes active per VALU instruction (PMC, profiles/r06_c5_pmc_*): the lanes without a leaf idled through
-// the two fp64 ray/triangle constructions of the lanes with one.
-#ifndef MSH_ALONG_PEND
-#define MSH_ALONG_PEND 1
-#endif
-#ifndef MSH_ALONG_LIST
-#define MSH_ALONG_LIST 0
-#endif
-constexpr int kAlongPend = MSH_ALONG_PEND;
-constexpr unsigned kARing = 256;  // ring entries per wave: < 64 left after a full round + <= 128 per step
-__device__ inline unsigned lanes_below_r(unsigned long long m) {
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
-template <bool STATS>
-__device__ inline void traverse_along_list(const BNode* __restrict__ nodes, size_t T, AlongPol& pol, bool active,
-                                           uint2* __restrict__ lds, uint2* __restrict__ spill, uint32_t* __restrict__ ring,
-                                           unsigned long long* __restrict__ bd, unsigned long long* __restrict__ bfl,
-                                           unsigned& n_nodes, unsigned& n_leaves) {
-    const int lane = threadIdx.x & 63;
-    int node = 0, sp = 0;
-    int nq = 0;             // this lane's entries appended since all of them were last evaluated (a bound)
-    unsigned last_pos = 0;  // ring counter of this lane's newest entry
-    unsigned head = 0, tail = 0;
-    size_t guard = 0;
-    if (active && T == 1) {  // a single leaf: no node to walk
-        node = ~0;
-    }
-    auto run_rounds = [&](unsigned upto) {
-        while (head != upto) {
-            const unsigned n = min(64u, upto - head);
-            bd[lane] = (unsigned long long)__double_as_longlong(pol.best);
-            bfl[lane] = ~0ull;
-            const bool valid = (unsigned)lane < n;
-            const uint32_t en = ring[(head + (valid ? (unsigned)lane : 0u)) & (kARing - 1)];
-            const int src = (int)(en & 63u);
-            const int leaf = (int)(en >> 6);
-            const D3 p = D3{__shfl(pol.p.x, src), __shfl(pol.p.y, src), __shfl(pol.p.z, src)};
-            const D3 nn = D3{__shfl(pol.n.x, src), __shfl(pol.n.y, src), __shfl(pol.n.z, src)};
-            D3 a, b, c;
-            uint32_t face;
-            load_tri(pol.tris, leaf, a, b, c, face);
-            double dist = INFINITY;
-#pragma nounroll
-            for (int k = 0; k < 2; ++k) {
-                D3 hit;
-                double dk;
-                if (AlongPol::along_pn(k, p, nn, a, b, c, hit, dk) && dk < dist) dist = dk;
-            }
-            const unsigned long long kb = (unsigned long long)__double_as_longlong(dist);
-            asm volatile("" ::: "memory");
-            if (valid && dist < INFINITY) atomicMin(&bd[src], kb);
-            asm volatile("" ::: "memory");
-            if (valid && dist < INFINITY && bd[src] == kb) atomicMin(&bfl[src], ((unsigned long long)face << 32) | (unsigned)leaf);
-            asm volatile("" ::: "memory");
-            const unsigned long long nb = bd[lane], nf = bfl[lane];
-            const double nd = __longlong_as_double((long long)nb);
-            const uint32_t nface = (uint32_t)(nf >> 32);
-            if (nf != ~0ull && (nd < pol.best || (nd == pol.best && nface < pol.best_face))) {
-                pol.best = nd;
-                pol.best_face = nface;
-                pol.best_leaf = (int)(uint32_t)nf;
-                pol.relim();
-            }
-            asm volatile("" ::: "memory");
-            if (STATS && valid) ++n_leaves;
-            head += n;
-        }
-        if ((int)(last_pos - head) < 0) nq = 0;  // every entry of this lane is evaluated
-    };
-    for (;;) {
-        const bool can = active && nq < kAlongPend;
-        const bool any = __ballot(can) != 0ull;
-        if (!any && tail == head) break;
-        int l0 = -1, l1 = -1;
-        if (can) {
-            if (node < 0) {  // a parked leaf (or the single leaf of a one-leaf tree)
-                l0 = ~node;
-                node = 0;
-                active = T > 1 && sp > 0;
-                if (active) {
-                    active = false;
-                    while (sp > 0) {
-                        --sp;
-                        const uint2 e = stack_get(lds, spill, sp);
-                        if (pol.keep(__uint_as_float(e.y))) {
-                            node = (int)e.x;
-                            active = true;
-                            break;
-                        }
-                    }
-                }
-            } else {
-                const NodeV nd = load_node(nodes, node);
-                if (STATS) ++n_nodes;
-                bool h0, h1;
-                float k0, k1;
-                pol.children(nd, h0, h1, k0, k1);
-                const int c0 = nd.child(0), c1 = nd.child(1);
-                const bool lf0 = h0 && c0 < 0, lf1 = h1 && c1 < 0;
-                const bool in0 = h0 && c0 >= 0, in1 = h1 && c1 >= 0;
-                if (lf0 && lf1 && nq + 1 >= kAlongPend) {  // room for one: queue the nearer, park the farther
-                    const bool first1 = k1 < k0;
-                    l0 = first1 ? ~c1 : ~c0;
-                    node = first1 ? c0 : c1;  // negative: a parked leaf, handed over by the next step
-                } else {
-                    if (lf0) l0 = ~c0;
-                    if (lf1) { if (l0 < 0) l0 = ~c1; else l1 = ~c1; }
-                    bool more = true;
-                    if (in0 && in1) {
-                        int nearc = c0, farc = c1;
-                        float kf = k1;
-                        if (k1 < k0) { nearc = c1; farc = c0; kf = k0; }
-                        stack_put(lds, spill, sp, make_uint2((unsigned)farc, __float_as_uint(kf)));
-                        ++sp;
-                        node = nearc;
-                    } else if (in0) {
-                        node = c0;
-                    } else if (in1) {
-                        node = c1;
-                    } else {
-                        more = false;
-                        while (sp > 0) {
-                            --sp;
-                            const uint2 e = stack_get(lds, spill, sp);
-                            if (pol.keep(__uint_as_float(e.y))) {
-                                node = (int)e.x;
-                                more = true;
-                                break;
-                            }
-                        }
-                    }
-                    active = more;
-                }
-                if (++guard >= T) active = false;  // each node is entered once: a corrupt tree
-            }
-        }
-        // append this step's leaves (at most two per lane) to the ring, in lane order
-        const unsigned long long m1 = __ballot(l0 >= 0), m2 = __ballot(l1 >= 0);
-        const unsigned pos = tail + lanes_below_r(m1) + lanes_below_r(m2);
-        if (l0 >= 0) {
-            ring[pos & (kARing - 1)] = ((uint32_t)l0 << 6) | (uint32_t)lane;
-            last_pos = pos;
-            ++nq;
-        }
-        if (l1 >= 0) {
-            ring[(pos + 1) & (kARing - 1)] = ((uint32_t)l1 << 6) | (uint32_t)lane;
-            last_pos = pos + 1;
-            ++nq;
-        }
-        tail += (unsigned)(__popcll(m1) + __popcll(m2));
-        const unsigned upto = any ? head + ((tail - head) & ~63u) : tail;
-        if (upto != head) run_rounds(upto);
-    }
-}
-
-// nearest_alongnormal with postponed leaf tests and no leaf list: a lane that reaches a leaf within reach keeps it
-// pending and stops; once every walking lane of the wave holds one, they all test their own leaf together (one call
-// site of the fp64 code), so the construction runs with every lane that has a leaf instead of one lane at a time.
-// A lane pends at most one leaf: its bound is never stale (the wave leaf list, which lets lanes walk on with up to
-// kAlongPend leaves waiting, walked 34.4 nodes per ray instead of 29.5 at kAlongPend >= 4; at 1 it ran 4.75 ms against
-// 5.02 for per-lane tests, profiles/r06_c5_along_list_pend_ab.jsonl, and this form needs neither its LDS ring nor the
-// owners' rows fetched by ds_bpermute).
 // The alongnormal kernel's LDS stack depth.  12 entries (24 KB per block) + the node slots (16 KB) would keep a block
 // at 40 KB, 4 blocks per CU: at 4 waves per SIMD (128 VGPRs, two reloads in the walk) C5 ran 4.53-4.61 ms against
 // 4.50-4.56 at 3 waves with 16 entries (profiles/r06_c5_along_waves_ab.jsonl).
@@ -399,25 +225,21 @@ __device__ inline void traverse_along_list(const BNode* __restrict__ nodes, size
 #define MSH_ALONG_STACK 16
 #endif
 constexpr int kAlongStack = MSH_ALONG_STACK;
-// visibility: the node prefetch into LDS with a 12-entry stack (24 KB + 16 KB of node slots per block: 4 blocks per
-// CU, the kernel's 4 waves per SIMD) measured 58.8-59.8 against 50.9-51.4 ms for C5's 160M rays
-// (profiles/r06_c5_vis_pf_ab.jsonl): off
-#ifndef MSH_VIS_PF
-#define MSH_VIS_PF 0
-#endif
-constexpr int kVisStack = MSH_VIS_PF ? 12 : kStack;
-// PF: the lane's next node is loaded into its LDS slot as soon as it is chosen (node_prefetch, as k_knn's list
-// path), so its latency overlaps the wave's leaf phases and the loop's bookkeeping
-#ifndef MSH_ALONG_PF
-#define MSH_ALONG_PF 1
-#endif
-#ifndef MSH_RAY_TILE_PF
-#define MSH_RAY_TILE_PF 1
-#endif
-// alongnormal walks start from the closest-point entry cut when the tree holds one (traverse_along_pend)
-#ifndef MSH_ALONG_CUT
-#define MSH_ALONG_CUT 1
-#endif
+// (visibility keeps the plain walk with kStack entries and no node slots: the node prefetch into LDS with a 12-entry
+// stack measured 58.8-59.8 against 50.9-51.4 ms for C5's 160M rays, profiles/r06_c5_vis_pf_ab.jsonl)
+
+// nearest_alongnormal with postponed leaf tests and no leaf list: a lane that reaches a leaf within reach keeps it
+// pending and stops; once every walking lane of the wave holds one, they all test their own leaf together (one call
+// site of the fp64 code), so the construction runs with every lane that has a leaf instead of one lane at a time
+// (per-lane leaf tests ran with 31 % of the lanes active per VALU instruction, PMC, profiles/r06_c5_pmc_*).
+// A lane pends at most one leaf: its bound is never stale (the wave leaf list, which lets lanes walk on with up to
+// N leaves waiting, walked 34.4 nodes per ray instead of 29.5 at N >= 4; at N = 1 it ran 4.75 ms against
+// 5.02 for per-lane tests, profiles/r06_c5_along_list_pend_ab.jsonl, and this form needs neither its LDS ring nor the
+// owners' rows fetched by ds_bpermute).  The list variant (traverse_along_list) was removed: it never learned the
+// entry cut (capf was not reset and no walk restarted from the root, so wrong answers on a tree that holds one) and
+// it used the default stack depth, overrunning LDS at MSH_ALONG_STACK < 16.
+// Each next node is loaded into the lane's LDS slot as soon as it is chosen (node_prefetch, as k_knn's list path), so
+// its latency overlaps the wave's leaf phases and the loop's bookkeeping.
 // rec / rho (round 6): the ray's cell of the closest-point entry cut and the radius around p its start list covers (every
 // subtree left out of it is farther than rho from p: k_rays).  The walk first runs from the list with the bound capped
 // at rho; a hit within rho is then the answer (every face with a hit that near lies in the list's subtrees, and they
@@ -436,7 +258,7 @@ __device__ inline void traverse_along_pend(const BNode* __restrict__ nodes, size
         active = false;
     }
     auto fetch = [&]() {
-        if (MSH_ALONG_PF && node >= 0) node_prefetch(nodes, node, wsl);
+        if (node >= 0) node_prefetch(nodes, node, wsl);
     };
     bool phase_a = false;
     if (active && rec) {  // the start list, nearest first: the first entry is the node, the others stacked (key 0)
@@ -489,7 +311,7 @@ __device__ inline void traverse_along_pend(const BNode* __restrict__ nodes, size
             pend = ~node;
             node = 0;
         } else {
-            const NodeV nd = MSH_ALONG_PF ? node_from_lds(nb) : load_node(nodes, node);
+            const NodeV nd = node_from_lds(nb);
             if (STATS) ++n_nodes;
             bool h0, h1;
             float k0, k1;
@@ -627,16 +449,11 @@ __device__ inline bool finite_d3(const D3& x) { return isfinite(x.x) && isfinite
 template <int MODE, bool STATS>  // MODE 0 alongnormal, 1 visibility
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MODE == 0 ? MSH_ALONG_WAVES : 4))) void k_rays(RayArgs a) {
     unsigned n_nodes = 0, n_leaves = 0;
-    __shared__ uint2 stk[(MODE == 0 ? kAlongStack : kVisStack) * kBlock];
-    // alongnormal: each wave's leaf ring + per-owner (distance bits, face << 32 | leaf) slots
-    __shared__ uint32_t rsh[MODE == 0 && MSH_ALONG_LIST ? 4 * (kARing + 64 * 4) : 1];
+    __shared__ uint2 stk[(MODE == 0 ? kAlongStack : kStack) * kBlock];
     const int tid = threadIdx.x, lane = tid & 63;
     uint2* lds = stk + tid;
-    uint32_t* ring = rsh + (MODE == 0 && MSH_ALONG_LIST ? (tid >> 6) * (kARing + 64 * 4) : 0);
-    [[maybe_unused]] unsigned long long* rbd = reinterpret_cast<unsigned long long*>(ring + kARing);
-    [[maybe_unused]] unsigned long long* rbfl = rbd + 64;
     // alongnormal: each wave's node slots (node_prefetch: LDS address from a wave-uniform index, so M0 is scalar)
-    constexpr bool kPF = MODE == 0 ? MSH_ALONG_PF : MSH_VIS_PF;
+    constexpr bool kPF = MODE == 0;
     __shared__ float4 nbuf[kPF ? 4 * kBlock : 1];
     const int wv_u = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t wsl = (uint32_t)(size_t)(__attribute__((address_space(3))) float4*)(nbuf + (kPF ? wv_u * 256 : 0));
@@ -644,25 +461,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MODE == 
     uint2* spill = a.spill ? a.spill + (size_t)blockIdx.x * kBlock * (size_t)a.spill_depth + tid : nullptr;
     const unsigned group = blockIdx.x & 7u;
     const D3 org = D3{a.org[0], a.org[1], a.org[2]};
-#if MSH_RAY_TILE_PF
-    // the next tile of the wave's group is claimed while the current one's rays load (nearest.hip MSH_TILE_PF)
+    // the next tile of the wave's group is claimed while the current one's rays load (as nearest.hip's kernels)
     const unsigned glo = (unsigned)(((unsigned long long)a.ntiles * group) >> 3);
     const unsigned ghi = (unsigned)(((unsigned long long)a.ntiles * (group + 1)) >> 3);
     unsigned nxt = ~0u;
-#endif
     for (;;) {
         unsigned tile = 0;
-#if MSH_RAY_TILE_PF
         if (lane == 0) tile = (nxt != ~0u && glo + nxt < ghi) ? glo + nxt : dequeue_tile_r(a.counters, a.ntiles, group);
-#else
-        if (lane == 0) tile = dequeue_tile_r(a.counters, a.ntiles, group);
-#endif
         tile = __shfl(tile, 0);
         if (tile >= a.ntiles) break;
         const size_t i = (size_t)tile * 64 + lane;
-#if MSH_RAY_TILE_PF
         if (lane == 0) nxt = glo < ghi ? atomicAdd(&a.counters[group * 32], 1u) : ~0u;
-#endif
         if (MODE == 0) {
             // every lane stays in the wave's loop (the leaf rounds use all 64); a lane past the rays only helps
             const bool live = i < a.S;
@@ -712,13 +521,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MODE == 
                     }
                 }
             }
-#if MSH_ALONG_LIST
-            traverse_along_list<STATS>(a.nodes, a.T, pol, live && finite_d3(p) && finite_d3(dp), lds, spill, ring, rbd,
-                                       rbfl, n_nodes, n_leaves);
-#else
             traverse_along_pend<STATS>(a.nodes, a.T, pol, go, lds, spill, n_nodes, n_leaves, nb, wsl, rec,
                                        a.cut_wide != 0, rho);
-#endif
             if (STATS || !live) continue;
             const double dist = pol.best == INFINITY ? 1e100 : pol.best;
             a.out_dist[r] = dist;  // scattered stores to the caller's row
@@ -741,7 +545,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MODE == 
             const D3 d = ray_dir(src, dir);
             AnyPol pol{a.tris, src, d, make_rayf(vsub(src, org), d, a.M, false), false};
             if (finite_d3(src) && finite_d3(d))
-                traverse_rays<AnyPol, STATS, kPF, kVisStack>(a.nodes, a.T, pol, lds, spill, n_nodes, n_leaves, nb, wsl);
+                traverse_rays<AnyPol, STATS>(a.nodes, a.T, pol, lds, spill, n_nodes, n_leaves);
             if (STATS) continue;
             const uint32_t reach = pol.hit ? 0u : 1u;
             a.ndc[o] = a.normals ? vdot(D3{a.normals[3 * iv], a.normals[3 * iv + 1], a.normals[3 * iv + 2]}, dir) : 0.0;
@@ -792,7 +596,7 @@ static int launch_rays(msh_tree* tree, RayArgs a, size_t nrays, hipStream_t s, c
     MSH_HIP(hipMemsetAsync(a.counters, 0, 8 * 32 * sizeof(unsigned), s));
     a.spill = nullptr;
     a.spill_depth = 0;
-    const int lds_depth = MODE == 0 ? kAlongStack : kVisStack;
+    const int lds_depth = MODE == 0 ? kAlongStack : kStack;
     const int need = tree->max_depth + 1 + (a.cut ? kCutK : 0);  // + the entry cut's start list
     if (need > lds_depth) {
         a.spill_depth = need - lds_depth + 1;
@@ -807,7 +611,7 @@ static int launch_rays(msh_tree* tree, RayArgs a, size_t nrays, hipStream_t s, c
 
 // the tree's closest-point entry cut for the alongnormal walks (traverse_along_pend's first phase)
 static void along_cut(const msh_tree* tree, RayArgs& a) {
-    if (!MSH_ALONG_CUT || !tree->d_cut || tree->B != 1 || tree->cut_G <= 0) return;
+    if (!tree->d_cut || tree->B != 1 || tree->cut_G <= 0) return;
     a.cut = tree->d_cut;
     a.cut_wide = tree->cut_wide;
     a.cut_G = tree->cut_G;

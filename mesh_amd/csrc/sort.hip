@@ -244,25 +244,23 @@ int radix_sort_pairs(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uint32_
 // Specialised for the query path (3 passes of 8 bits, values = row indices), so the passes move fewer bytes than
 // radix_sort_pairs does with the same ballot ranking:
 //   k_qkeys      Morton key of every row + the first pass's per-tile digit counts (no separate histogram read);
-//   pass 1       u32 keys in, rows implied by the index (no value array is written or read), packed u64 out
-//                (key << 32 | row: one 8-B store per element, so a digit run of a tile is twice as long in
-//                bytes as two 4-B arrays);
-//   pass 2       packed in, packed out;   pass 3  packed in, rows only out (the keys are not needed after it).
-// Tiles of kQsNT x 16 elements: with 512-thread blocks a tile's 256 digit runs average 32 elements (256 B
-// packed), so the scattered stores are mostly whole lines.  HBM bytes per element: 24 (rows) + 4 (keys) in
-// k_qkeys; 4 + 8 in pass 1; 8 (histogram) + 8 + 8 in pass 2; 8 + 8 + 4 in pass 3.
+//   pass 1       u32 keys in, rows implied by the index (no value array is read), keys and rows out;
+//   pass 2       keys and rows in, keys and rows out;   pass 3  keys and rows in, rows only out (the keys are not
+//                needed after it).
+// Keys and rows travel in two u32 arrays (the two halves of keys_alt, then of vals_alt), so a histogram pass
+// (k_qhist32) reads the 4-B keys alone.  Tiles of kQsNT x 16 elements: with 512-thread blocks a tile's 256 digit runs
+// average 32 elements (128 B per array).  HBM bytes per element: 24 (rows) + 4 (keys) in k_qkeys; 4 + 8 in pass 1;
+// 4 (histogram) + 8 + 8 in pass 2; 4 + 8 + 4 in pass 3.
 // 512-thread blocks, 8192-key tiles: 73 KB of LDS, so two blocks per CU overlap each other's load, rank and write
 // phases (1024 threads and 16384-key tiles took 145 KB, one block per CU): C3 100M rows 1.94-1.98 -> 1.77 ms per sort,
 // 12.5M rows 0.267 -> 0.226 ms (profiles/r05_ab_sort_fold_nt.jsonl); a stable sort, so the same order either way
 #ifndef MSH_QSORT_NT
 #define MSH_QSORT_NT 512
 #endif
-// Query order along the Hilbert curve of the 256^3 cells instead of the Morton curve: C3 100M 1985-1990 ->
-// 2033-2058 M q/s, 12.5M rows 1390 -> 1401-1416 M q/s (profiles/r05_ab_leaders_sort_resume.jsonl)
-#ifndef MSH_QORDER_HILBERT
-#define MSH_QORDER_HILBERT 1
-#endif
 constexpr int kQsNT = MSH_QSORT_NT;
+
+// The query order runs along the Hilbert curve of the 256^3 cells, not the Morton curve: C3 100M 1985-1990 ->
+// 2033-2058 M q/s, 12.5M rows 1390 -> 1401-1416 M q/s (profiles/r05_ab_leaders_sort_resume.jsonl).
 
 // 24-bit Hilbert index of a cell of the 256^3 grid: Skilling's transform ("Programming the Hilbert curve", 2004: the
 // axes to the transposed form, then the transposed bits interleaved, axis 0 first at each level; numpy copy in
@@ -371,10 +369,10 @@ __global__ __launch_bounds__(NT) void k_qkeys(const double* __restrict__ q, size
                                               uint32_t* __restrict__ hist, unsigned nb) {
     constexpr int NW = NT / 64;
     __shared__ uint32_t h[NW][256];
-    __shared__ uint16_t pairs[MSH_QORDER_HILBERT ? kHilbertPairs : 1];
+    __shared__ uint16_t pairs[kHilbertPairs];
     const int tid = threadIdx.x, w = tid >> 6;
     for (int i = tid; i < NW * 256; i += NT) (&h[0][0])[i] = 0;
-    if (MSH_QORDER_HILBERT) hilbert_pairs(pairs, tid, NT);
+    hilbert_pairs(pairs, tid, NT);
     __syncthreads();
     const size_t base = (size_t)blockIdx.x * (NT * ITEMS);
 #pragma unroll 4
@@ -382,7 +380,7 @@ __global__ __launch_bounds__(NT) void k_qkeys(const double* __restrict__ q, size
         const size_t i = base + (size_t)k * NT + tid;
         if (i < n) {
             uint32_t key = query_morton30(q[3 * i], q[3 * i + 1], q[3 * i + 2], lx, ly, lz, hx, hy, hz) >> lo_bit;
-            if (MSH_QORDER_HILBERT) key = hilbert24(key, pairs);  // the same 256^3 cells (lo_bit == 6), Hilbert order
+            key = hilbert24(key, pairs);  // the same 256^3 cells (lo_bit == 6), Hilbert order
             keys[i] = key;
             atomicAdd(&h[w][key & 255u], 1u);
         }
@@ -396,8 +394,9 @@ __global__ __launch_bounds__(NT) void k_qkeys(const double* __restrict__ q, size
     }
 }
 
+// Digit counts of a middle pass, from the keys alone.
 template <int NT, int ITEMS>
-__global__ __launch_bounds__(NT) void k_qhist64(const unsigned long long* __restrict__ in, size_t n, int shift,
+__global__ __launch_bounds__(NT) void k_qhist32(const uint32_t* __restrict__ keys, size_t n, int shift,
                                                 uint32_t* __restrict__ hist, unsigned nb) {
     constexpr int NW = NT / 64;
     __shared__ uint32_t h[NW][256];
@@ -405,15 +404,15 @@ __global__ __launch_bounds__(NT) void k_qhist64(const unsigned long long* __rest
     for (int i = tid; i < NW * 256; i += NT) (&h[0][0])[i] = 0;
     __syncthreads();
     const size_t base = (size_t)blockIdx.x * (NT * ITEMS);
-    unsigned long long e[ITEMS];
+    uint32_t e[ITEMS];
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k) {
         const size_t i = base + (size_t)k * NT + tid;
-        e[k] = i < n ? in[i] : ~0ull;
+        e[k] = i < n ? keys[i] : 0xFFFFFFFFu;
     }
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k)
-        if (e[k] != ~0ull) atomicAdd(&h[w][(uint32_t)(e[k] >> (32 + shift)) & 255u], 1u);
+        if (e[k] != 0xFFFFFFFFu) atomicAdd(&h[w][(e[k] >> shift) & 255u], 1u);
     __syncthreads();
     for (int d = tid; d < 256; d += NT) {
         uint32_t c = 0;
@@ -423,14 +422,15 @@ __global__ __launch_bounds__(NT) void k_qhist64(const unsigned long long* __rest
     }
 }
 
-// One stable pass on digit (key >> shift) & 255.  IN64: packed input, else u32 keys whose row is the index.
-// OUT64: packed output, else the rows only.  Ranking as k_scatter: eight ballots per element give its rank among
-// the wave's equal digits; per-wave digit counts are scanned over the block, the tile is staged in LDS in its
-// sorted order and written out linearly (each digit run of the tile contiguous).
-template <int NT, int ITEMS, bool IN64, bool OUT64>
-__global__ __launch_bounds__(NT) void k_qscatter(const void* __restrict__ in, void* __restrict__ out, size_t n, int shift,
-                                                 const uint32_t* __restrict__ offs, unsigned nb,
-                                                 const uint32_t* __restrict__ sums, unsigned nsums) {
+// One stable pass on digit (key >> shift) & 255.  ROWS_IN: rows from rin (else the index); KEYS_OUT: keys written to
+// kout (else the rows only).  Ranking as k_scatter: eight ballots per element give its rank among the wave's equal
+// digits; per-wave digit counts are scanned over the block, the tile is staged in LDS in its sorted order (key << 32 |
+// row) and written out linearly (each digit run of the tile contiguous).
+template <int NT, int ITEMS, bool ROWS_IN, bool KEYS_OUT>
+__global__ __launch_bounds__(NT) void k_qscatter2(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ rin,
+                                                  uint32_t* __restrict__ kout, uint32_t* __restrict__ rout, size_t n,
+                                                  int shift, const uint32_t* __restrict__ offs, unsigned nb,
+                                                  const uint32_t* __restrict__ sums, unsigned nsums) {
     constexpr int NW = NT / 64, TILE = NT * ITEMS, WI = 64 * ITEMS;
     static_assert(NT >= 256, "one thread per digit");
     __shared__ uint32_t wcnt[NW][256];
@@ -442,14 +442,12 @@ __global__ __launch_bounds__(NT) void k_qscatter(const void* __restrict__ in, vo
     const size_t tile0 = (size_t)blockIdx.x * TILE;
     const size_t base = tile0 + (size_t)w * WI;
     const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    const unsigned long long* in64 = static_cast<const unsigned long long*>(in);
-    const uint32_t* in32 = static_cast<const uint32_t*>(in);
     unsigned long long ee[ITEMS];
     uint32_t rr[ITEMS];
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) {
         const size_t i = base + (size_t)it * 64 + lane;
-        ee[it] = i < n ? (IN64 ? in64[i] : (((unsigned long long)in32[i] << 32) | (uint32_t)i)) : 0ull;
+        ee[it] = i < n ? (((unsigned long long)kin[i] << 32) | (ROWS_IN ? rin[i] : (uint32_t)i)) : 0ull;
     }
     // after the tile's loads are issued, so the offsets' loads and scan overlap them (its barriers also order
     // the counters' zeroing before the ranking)
@@ -507,128 +505,10 @@ __global__ __launch_bounds__(NT) void k_qscatter(const void* __restrict__ in, vo
     for (uint32_t p = tid; p < tn; p += NT) {
         const unsigned long long e = stage[p];
         const uint32_t dst = gbase[(uint32_t)(e >> (32 + shift)) & 255u] + p;
-        if (OUT64) static_cast<unsigned long long*>(out)[dst] = e;
-        else static_cast<uint32_t*>(out)[dst] = (uint32_t)e;
-    }
-}
-
-// Split-array form of the middle passes (MSH_QSORT_SPLIT): keys and rows in two u32 arrays, so a histogram pass
-// reads 4 B per element instead of the packed 8 B (a digit run of an 8192-key tile averages 128 B per array).
-template <int NT, int ITEMS>
-__global__ __launch_bounds__(NT) void k_qhist32(const uint32_t* __restrict__ keys, size_t n, int shift,
-                                                uint32_t* __restrict__ hist, unsigned nb) {
-    constexpr int NW = NT / 64;
-    __shared__ uint32_t h[NW][256];
-    const int tid = threadIdx.x, w = tid >> 6;
-    for (int i = tid; i < NW * 256; i += NT) (&h[0][0])[i] = 0;
-    __syncthreads();
-    const size_t base = (size_t)blockIdx.x * (NT * ITEMS);
-    uint32_t e[ITEMS];
-#pragma unroll
-    for (int k = 0; k < ITEMS; ++k) {
-        const size_t i = base + (size_t)k * NT + tid;
-        e[k] = i < n ? keys[i] : 0xFFFFFFFFu;
-    }
-#pragma unroll
-    for (int k = 0; k < ITEMS; ++k)
-        if (e[k] != 0xFFFFFFFFu) atomicAdd(&h[w][(e[k] >> shift) & 255u], 1u);
-    __syncthreads();
-    for (int d = tid; d < 256; d += NT) {
-        uint32_t c = 0;
-#pragma unroll
-        for (int x = 0; x < NW; ++x) c += h[x][d];
-        hist[(size_t)d * nb + blockIdx.x] = c;
-    }
-}
-
-// ROWS_IN: rows from rin (else the index); KEYS_OUT: keys written to kout (else the rows only).  Staged and ranked as
-// k_qscatter.
-template <int NT, int ITEMS, bool ROWS_IN, bool KEYS_OUT>
-__global__ __launch_bounds__(NT) void k_qscatter2(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ rin,
-                                                  uint32_t* __restrict__ kout, uint32_t* __restrict__ rout, size_t n,
-                                                  int shift, const uint32_t* __restrict__ offs, unsigned nb,
-                                                  const uint32_t* __restrict__ sums, unsigned nsums) {
-    constexpr int NW = NT / 64, TILE = NT * ITEMS, WI = 64 * ITEMS;
-    static_assert(NT >= 256, "one thread per digit");
-    __shared__ uint32_t wcnt[NW][256];
-    __shared__ uint32_t gbase[256];
-    __shared__ uint32_t ssum[4];
-    __shared__ unsigned long long stage[TILE];
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    for (int i = tid; i < NW * 256; i += NT) (&wcnt[0][0])[i] = 0;
-    const size_t tile0 = (size_t)blockIdx.x * TILE;
-    const size_t base = tile0 + (size_t)w * WI;
-    const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    unsigned long long ee[ITEMS];
-    uint32_t rr[ITEMS];
-#pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-        const size_t i = base + (size_t)it * 64 + lane;
-        ee[it] = i < n ? (((unsigned long long)kin[i] << 32) | (ROWS_IN ? rin[i] : (uint32_t)i)) : 0ull;
-    }
-    // after the tile's loads are issued, so the offsets' loads and scan overlap them (its barriers also order
-    // the counters' zeroing before the ranking)
-    const uint32_t g_off = tile_offset<NT>(offs, nb, sums, nsums, reinterpret_cast<uint32_t*>(stage));
-#pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-        const size_t i = base + (size_t)it * 64 + lane;
-        const bool valid = i < n;
-        const uint32_t d = (uint32_t)(ee[it] >> (32 + shift)) & 255u;
-        unsigned long long peers = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const bool bit = (d >> b) & 1u;
-            const unsigned long long m = __ballot(bit);
-            peers &= bit ? m : ~m;
-        }
-        const uint32_t prev = valid ? wcnt[w][d] : 0u;
-        if (valid && (peers & lt) == 0ull) wcnt[w][d] = prev + (uint32_t)__popcll(peers);
-        rr[it] = prev + (uint32_t)__popcll(peers & lt);
-    }
-    __syncthreads();
-    uint32_t tot = 0;
-    if (tid < 256) {
-#pragma unroll
-        for (int x = 0; x < NW; ++x) tot += wcnt[x][tid];
-    }
-    uint32_t incl = tot;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += y;
-    }
-    if (w < 4 && lane == 63) ssum[w] = incl;
-    __syncthreads();
-    if (tid < 256) {
-        uint32_t run = incl - tot;
-        for (int k = 0; k < w; ++k) run += ssum[k];
-        gbase[tid] = g_off - run;
-#pragma unroll
-        for (int x = 0; x < NW; ++x) {
-            const uint32_t c = wcnt[x][tid];
-            wcnt[x][tid] = run;
-            run += c;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-        const size_t i = base + (size_t)it * 64 + lane;
-        if (i < n) stage[wcnt[w][(uint32_t)(ee[it] >> (32 + shift)) & 255u] + rr[it]] = ee[it];
-    }
-    __syncthreads();
-    const uint32_t tn = (uint32_t)(n - tile0 < (size_t)TILE ? n - tile0 : (size_t)TILE);
-    for (uint32_t p = tid; p < tn; p += NT) {
-        const unsigned long long e = stage[p];
-        const uint32_t dst = gbase[(uint32_t)(e >> (32 + shift)) & 255u] + p;
         if (KEYS_OUT) kout[dst] = (uint32_t)(e >> 32);
         rout[dst] = (uint32_t)e;
     }
 }
-
-#ifndef MSH_QSORT_SPLIT
-#define MSH_QSORT_SPLIT 1
-#endif
 
 int query_sort(const float* lo, const float* hi, const double* d_q, size_t S, int lo_bit, Workspace& ws, hipStream_t s) {
     if (S == 0) return MSH_OK;
@@ -643,8 +523,6 @@ int query_sort(const float* lo, const float* hi, const double* d_q, size_t S, in
     MSH_TRY(ws.vals_alt.reserve(S * sizeof(unsigned long long)));
     MSH_TRY(ws.hist.reserve((size_t)nb * 256 * sizeof(uint32_t)));
     uint32_t* hist = ws.hist.as<uint32_t>();
-    unsigned long long* A = ws.keys_alt.as<unsigned long long>();
-    unsigned long long* B = ws.vals_alt.as<unsigned long long>();
     {
         TimedLaunch tl("morton", s);
         k_qkeys<kQsNT, kQsItems><<<nb, kQsNT, 0, s>>>(d_q, S, lo_bit, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2],
@@ -655,38 +533,23 @@ int query_sort(const float* lo, const float* hi, const double* d_q, size_t S, in
     const uint32_t* sums;
     unsigned nsums;
     MSH_TRY(scan_chunks(hist, (size_t)nb * 256, ws, s, &sums, &nsums, kQsMaxSums));
-    if (MSH_QSORT_SPLIT) {
-        uint32_t* k0 = ws.keys.as<uint32_t>();
-        uint32_t* k1 = ws.keys_alt.as<uint32_t>();
-        uint32_t* r1 = k1 + S;
-        uint32_t* k2 = ws.vals_alt.as<uint32_t>();
-        uint32_t* r2 = k2 + S;
-        k_qscatter2<kQsNT, kQsItems, false, true><<<nb, kQsNT, 0, s>>>(k0, nullptr, k1, r1, S, 0, hist, nb, sums, nsums);
-        MSH_HIP(hipGetLastError());
-        k_qhist32<kQsNT, kQsItems><<<nb, kQsNT, 0, s>>>(k1, S, 8, hist, nb);
-        MSH_HIP(hipGetLastError());
-        MSH_TRY(scan_chunks(hist, (size_t)nb * 256, ws, s, &sums, &nsums, kQsMaxSums));
-        k_qscatter2<kQsNT, kQsItems, true, true><<<nb, kQsNT, 0, s>>>(k1, r1, k2, r2, S, 8, hist, nb, sums, nsums);
-        MSH_HIP(hipGetLastError());
-        k_qhist32<kQsNT, kQsItems><<<nb, kQsNT, 0, s>>>(k2, S, 16, hist, nb);
-        MSH_HIP(hipGetLastError());
-        MSH_TRY(scan_chunks(hist, (size_t)nb * 256, ws, s, &sums, &nsums, kQsMaxSums));
-        k_qscatter2<kQsNT, kQsItems, true, false><<<nb, kQsNT, 0, s>>>(k2, r2, nullptr, ws.vals.as<uint32_t>(), S, 16,
-                                                                        hist, nb, sums, nsums);
-        MSH_HIP(hipGetLastError());
-        return MSH_OK;
-    }
-    k_qscatter<kQsNT, kQsItems, false, true><<<nb, kQsNT, 0, s>>>(ws.keys.ptr, A, S, 0, hist, nb, sums, nsums);
+    uint32_t* k0 = ws.keys.as<uint32_t>();
+    uint32_t* k1 = ws.keys_alt.as<uint32_t>();
+    uint32_t* r1 = k1 + S;
+    uint32_t* k2 = ws.vals_alt.as<uint32_t>();
+    uint32_t* r2 = k2 + S;
+    k_qscatter2<kQsNT, kQsItems, false, true><<<nb, kQsNT, 0, s>>>(k0, nullptr, k1, r1, S, 0, hist, nb, sums, nsums);
     MSH_HIP(hipGetLastError());
-    k_qhist64<kQsNT, kQsItems><<<nb, kQsNT, 0, s>>>(A, S, 8, hist, nb);
+    k_qhist32<kQsNT, kQsItems><<<nb, kQsNT, 0, s>>>(k1, S, 8, hist, nb);
     MSH_HIP(hipGetLastError());
     MSH_TRY(scan_chunks(hist, (size_t)nb * 256, ws, s, &sums, &nsums, kQsMaxSums));
-    k_qscatter<kQsNT, kQsItems, true, true><<<nb, kQsNT, 0, s>>>(A, B, S, 8, hist, nb, sums, nsums);
+    k_qscatter2<kQsNT, kQsItems, true, true><<<nb, kQsNT, 0, s>>>(k1, r1, k2, r2, S, 8, hist, nb, sums, nsums);
     MSH_HIP(hipGetLastError());
-    k_qhist64<kQsNT, kQsItems><<<nb, kQsNT, 0, s>>>(B, S, 16, hist, nb);
+    k_qhist32<kQsNT, kQsItems><<<nb, kQsNT, 0, s>>>(k2, S, 16, hist, nb);
     MSH_HIP(hipGetLastError());
     MSH_TRY(scan_chunks(hist, (size_t)nb * 256, ws, s, &sums, &nsums, kQsMaxSums));
-    k_qscatter<kQsNT, kQsItems, true, false><<<nb, kQsNT, 0, s>>>(B, ws.vals.ptr, S, 16, hist, nb, sums, nsums);
+    k_qscatter2<kQsNT, kQsItems, true, false><<<nb, kQsNT, 0, s>>>(k2, r2, nullptr, ws.vals.as<uint32_t>(), S, 16, hist,
+                                                                    nb, sums, nsums);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }

@@ -14,11 +14,12 @@ reloads, so a variant with loop spills is not worth a GPU session.
 --save FILE only writes the assembly; --diff FILE (the --save of another tree) compares the two kernel by kernel instead
 of reporting -- the .amdhsa_* block and the instruction text, comments dropped and labels renumbered -- and exits 1
 when any kernel differs.  Two compiles of one source differ only in the __hip_cuid_* symbol, so a refactor that should
-not touch the generated code shows "identical" for every kernel.  A tree from before these options gets a copy of this
-script first (it compiles the nearest.hip beside it):
+not touch the generated code shows "identical" for every kernel.  Both take --src FILE, the source of mesh_amd/csrc to
+compile (default nearest.hip; the report is of nearest.hip's kernels only).  A tree from before these options gets a
+copy of this script first (it compiles the sources beside it):
 
-    cp scripts/isa_check.py ../parent/scripts/ && python ../parent/scripts/isa_check.py --save /tmp/parent.s
-    python scripts/isa_check.py --diff /tmp/parent.s
+    cp scripts/isa_check.py ../parent/scripts/ && python ../parent/scripts/isa_check.py --src rays.hip --save /tmp/parent.s
+    python scripts/isa_check.py --src rays.hip --diff /tmp/parent.s
 """
 import os
 import re
@@ -27,14 +28,14 @@ import sys
 import tempfile
 
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(R, "mesh_amd", "csrc", "nearest.hip")
+CSRC = os.path.join(R, "mesh_amd", "csrc")
 
 
-def compile_asm(flags):
+def compile_asm(flags, src="nearest.hip"):
     out = tempfile.NamedTemporaryFile(suffix=".s", delete=False).name
     cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950",
-           "--cuda-device-only", "-S", SRC, "-o", out] + flags
-    subprocess.run(cmd, check=True, cwd=os.path.dirname(SRC), stderr=subprocess.DEVNULL)
+           "--cuda-device-only", "-S", os.path.join(CSRC, src), "-o", out] + flags
+    subprocess.run(cmd, check=True, cwd=CSRC, stderr=subprocess.DEVNULL)
     with open(out) as f:
         s = f.read()
     os.unlink(out)
@@ -201,13 +202,19 @@ def diff(s, other):
 def main():
     flags = sys.argv[1:]
     save = other = None
+    src = "nearest.hip"
+    if "--src" in flags:  # with --save / --diff: another source of mesh_amd/csrc
+        src = os.path.basename(flags.pop(flags.index("--src") + 1))
+        flags.remove("--src")
+        if src != "nearest.hip" and "--save" not in flags and "--diff" not in flags:
+            sys.exit("--src goes with --save or --diff: the report is of nearest.hip's kernels")
     if "--save" in flags:  # keep the assembly, for another tree's --diff
         save = flags.pop(flags.index("--save") + 1)
         flags.remove("--save")
     if "--diff" in flags:
         other = flags.pop(flags.index("--diff") + 1)
         flags.remove("--diff")
-    s = compile_asm(flags)
+    s = compile_asm(flags, src)
     if save:
         with open(save, "w") as f:
             f.write(s)
