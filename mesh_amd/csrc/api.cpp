@@ -513,9 +513,13 @@ static void free_entry_cut(msh_tree* t) {
 // The automatic grid comes in two sizes (round 6).  A coarse grid, 8 cells per leaf (at most 2^23 cells; C3: G = 200,
 // 256 MB), is built by the call that brings the handle's rows to 1/16 of its cells (C3: 500k rows); it costs a
 // one-shot caller ~10 ms.  The fine grid, 64 cells per leaf (at most 2^26; C3: G = 400, 2.05 GB), replaces it once the
-// handle has answered kFineRowsPerCell rows per fine cell (C3: ~1G rows): its ~46-ms build pays back after that many
-// queries (C3 100M-query batches: ~3 ms faster each than with the coarse grid).  msh_tree_set_entry_cut(t, -1) asks
-// for the fine grid at the next call (a caller that keeps the tree for many batches, as bench.py does).
+// handle has answered kFineRowsPerCell rows per fine cell (C3: ~1G rows): its build (round 6: ~46 ms; ~113 ms with
+// round 8's directional drop) pays back after that many queries (C3 100M-query batches: ~3 ms faster each than with
+// the coarse grid, ~6 with the drop).  msh_tree_set_entry_cut(t, -1) asks for the fine grid at the next call (a caller
+// that keeps the tree for many batches, as bench.py does).  The volume threshold is sized for that build, so the
+// upgrade the policy makes on its own keeps the directional drop on whole cells (depth 0); the sub-cell depths of round
+// 12, whose build is 6 / 27 times longer (C3: 0.66 / 3.05 s for 1.5 / 2.6 ms more per batch), go to the grids a caller
+// asked for (build_entry_cut).
 // Round-5 figures (68-B cells of 8 entries and a separate hint), C3 in M q/s: 8 per leaf, 2^23 cells: G = 200, 46.9
 // node visits per query, 2156-2213; 16, 2^25: G = 252, 45.2 visits, 2238; 32, 2^25: G = 318, 43.6 visits, 2247-2290
 // (profiles/r05_ab_noleaders_cut.jsonl); in another session 32: 2261-2286, 64, 2^26: G = 400, 42.2 visits,
@@ -554,7 +558,8 @@ static int cut_grid(const msh_tree* t, bool fine) {
 // coarsest grid answered exactly, each finer level cut from the coarser one's records with hints taken from the 8
 // coarse cells around it -- which built C3's grid in 41 ms instead of ~70 but started queries from worse hints:
 // 49.4 node visits per query against 42.5, 2.02-2.06 G q/s against 2.32-2.36 (profiles/r06_c3_cut_levels_ab.jsonl).
-static int build_entry_cut(msh_tree* t, bool fine) {
+// subdiv: the sub-cell depth of the directional drop, where the grid takes the drop at all (nearest.hip cut_dir_drop).
+static int build_entry_cut(msh_tree* t, bool fine, int subdiv) {
     const int G = cut_grid(t, fine);
     double half[3], H = 0.0, lo[3], w[3];
     for (int k = 0; k < 3; ++k) {
@@ -578,10 +583,13 @@ static int build_entry_cut(msh_tree* t, bool fine) {
     }
     const bool e4 = t->T <= kEnt4MaxLeaves;
     const size_t rb = cut_rec_bytes(t);
-    // the directional drop triples the cut launch (fp64 work per kept child: C3 coarse 3.7 -> 11.2 ms, fine 22 -> 81 ms),
-    // which a kept tree's batches repay (C3 G = 400: 42.4 -> 34.0 node visits per query) and a one-shot caller's single
-    // batch on the automatic coarse grid does not (G = 200: 47.0 -> 41.6 visits, ~2 ms of 100M rows for +8 ms of build):
-    // the fine grid and a grid the caller asked for take it, the automatic coarse grid keeps the ball rule alone
+    // the directional drop on whole cells triples the cut launch (fp64 work per kept child: C3 coarse 3.7 -> 11.2 ms,
+    // fine 22 -> 81 ms; 76 ms at round 12's parent), which a kept tree's batches repay within ~20 (C3 G = 400: 42.4 ->
+    // 34.0 node visits per query) and a one-shot caller's single batch on the automatic coarse grid does not (G = 200:
+    // 47.0 -> 41.6 visits, ~2 ms of 100M rows for +8 ms of build): the fine grid and a grid the caller asked for take it,
+    // the automatic coarse grid keeps the ball rule alone.  Proved on sub-cells (subdiv 1 / 2) the fine launch takes
+    // 0.6 / 3.0 s on C3 for 29.6 / 26.6 visits, repaid after ~355 / ~1120 batches of 100M rows: the caller's choice
+    // (ensure_entry_cut), never the automatic upgrade's
     const bool directional = fine || t->cut_req > 0;
     hipStream_t s = t->stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -631,7 +639,7 @@ static int build_entry_cut(msh_tree* t, bool fine) {
                 t->cut_lo[0] == lo[0] && t->cut_lo[1] == lo[1] && t->cut_lo[2] == lo[2])
                 half = t->d_cut;
             if ((st = cut_level(t, G, lo, w, dp.as<double>(), dhint.as<int>(), cut, e4, s, half,
-                                dflag.as<unsigned long long>(), directional)) != MSH_OK)
+                                dflag.as<unsigned long long>(), directional ? subdiv : -1)) != MSH_OK)
                 break;
             (void)hipEventRecord(e1, s);
             unsigned long long nflag = 0;
@@ -699,7 +707,7 @@ static void ensure_entry_cut(msh_tree* t, size_t S) {
     double staged_ms = 0.0;
     if (fine && !t->d_cut && t->cut_req < 0) {
         t->cut_state = kCutOff;
-        if (build_entry_cut(t, false) == MSH_OK) {
+        if (build_entry_cut(t, false, 0) == MSH_OK) {
             staged_ms = t->cut_ms;
         } else {
             (void)hipGetLastError();  // the fine grid is then built from the root
@@ -718,7 +726,8 @@ static void ensure_entry_cut(msh_tree* t, size_t S) {
         old_iw[k] = t->cut_iw[k];
     }
     t->cut_state = kCutOff;
-    const int st = build_entry_cut(t, fine);
+    // a grid the caller asked for (msh_tree_set_entry_cut) takes the sub-cell depth; the policy's own upgrade does not
+    const int st = build_entry_cut(t, fine, automatic ? 0 : kCutSubdivDefault);
     if (st == MSH_OK) {
         t->cut_ms += staged_ms;
         if (old) {

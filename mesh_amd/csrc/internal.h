@@ -255,11 +255,15 @@ constexpr size_t kEnt4MaxLeaves = (size_t)1 << 20;  // 4-B stack / cut entries: 
 constexpr uint32_t kCutDirFlag = 0x40000000u;
 int cut_centres(int G, const double* lo, const double* w, double* d_q, hipStream_t s);
 // d_half: the records of the G/2 grid over the same box (same record size), each cell then starts from its enclosing
-// half-resolution cell's entries instead of the root; nullptr: from the root.  directional: also apply the
-// directional drop; d_nflag (nullable): incremented by the number of records it shortened
+// half-resolution cell's entries instead of the root; nullptr: from the root.  subdiv >= 0: also apply the
+// directional drop, proved on sub-cells down to that depth (0: whole cells only; at most kCutSubdiv; the test hook
+// MESH_AMD_CUT_SUBDIV = 0 / 1 / 2 overrides it); < 0: the ball rule alone.  d_nflag (nullable): incremented by the
+// number of records the drop shortened
+constexpr int kCutSubdiv = 2;         // the deepest split of a cell into octants
+constexpr int kCutSubdivDefault = 2;  // the depth of a grid the caller asked for (api.cpp ensure_entry_cut)
 int cut_level(const msh_tree* tree, int G, const double* lo, const double* w, const double* d_pts, const int* d_hint,
               uint32_t* d_rec, bool e4, hipStream_t s, const uint32_t* d_half = nullptr,
-              unsigned long long* d_nflag = nullptr, bool directional = true);
+              unsigned long long* d_nflag = nullptr, int subdiv = 0);
 // d_inv[face] = the leaf holding it (T words)
 int face_leaf_map(const msh_tree* tree, uint32_t* d_inv, hipStream_t s);
 // closest point (and part) of each row q[i] on face d_face[i] (the traversal's answer construction); d_inv from

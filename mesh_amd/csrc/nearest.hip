@@ -2147,7 +2147,10 @@ __global__ __launch_bounds__(kBlock) void k_cut_centres(int G, double lx, double
 // rounded down to fp32, s = sqrt(bound) (1 - 1e-5) - r (1 + 1e-5): a lower bound of the squared distance from any q
 // of the cell.
 //
-// The directional drop (cut_dir_drop).  The ball rule is the triangle inequality on two distances from c; it ignores
+// The directional drop (cut_dir_drop; DIR launches: the fine grid and grids a caller asked for).  A child the ball
+// rule kept is tried on the whole cell and, when that fails, piece by piece on the cell's octants and their octants
+// (round 12, "Sub-cells" below; the depth is a launch argument, MESH_AMD_CUT_SUBDIV in cut_level).
+// The ball rule is the triangle inequality on two distances from c; it ignores
 // that, as q moves in the cell, the distance to a box B and the distance to c's closest point pc move almost together.
 // Let a_k (k = 0, 1, 2) be the node's fp32 frame rows (n, t, b = n x t as frame_b rounds it) taken as exact reals, A
 // the matrix of these rows, o the tree origin, and B = {x : lo_k <= a_k . (x - o) <= hi_k} the child's decoded box: a
@@ -2180,54 +2183,138 @@ __global__ __launch_bounds__(kBlock) void k_cut_centres(int G, double lx, double
 // directional drop breaks: such a record is flagged -- kCutDirFlag in word 0 of a 32-B record, word 1 (the radius) 0
 // in a 64-B one -- and inherits the flag of the coarse record it starts from; a ray in a flagged cell starts at the
 // root.  The closest-point walks mask the flag (cut_hint_leaf).  nflag: the number of flagged cells.
-// Both children at once (they share the frame and c's projections); h0 / h1: in, the child passed the ball rule; out,
-// it also survives this one.  r2p = 2 r^2 / d_p.  Returns whether a child was dropped.
-__device__ inline bool cut_dir_drop(const NodeV& nd, bool& h0, bool& h1, const D3& co, const D3& vp, double dp, double r,
-                                    double r2p, double mag) {
+//
+// Sub-cells (round 12).  Nothing above uses that the expansion point is the cell's centre, nor that pc is that point's
+// own closest point.  For any point x0 and radius rho, with d_B = D(x0) > rho (1 + 1e-5) and
+// d_p = |x0 - pc| > rho (1 + 1e-5), the same integration along the segments from x0 gives
+//   F(q) >= F(x0) - rho (|grad F(x0)| + 4 rho / d_B + 2 rho / d_p)   for every q within rho of x0,
+// and the last step needs of pc only that it is a point of the mesh: |q - pc| >= d(q), so F(q) > m still gives
+// dist(q, any face below the child) > d(q) + m.  The first-order term halves with rho and the other two quarter, so a
+// child the whole cell cannot drop may still be dropped piece by piece: when the test fails on (c, r) it is tried on
+// the cell's 8 octants -- centres c +- w / 4 per axis, radius r / 2 -- and an octant that fails on its own 8 octants
+// (radius r / 4), down to depth kCutSubdiv; the child is dropped only if every piece proves it.  The pieces' balls
+// cover what the cell's ball had to: an octant's half-diagonal is |w| / 4 and its ball's radius |w| / 4 + 0.1 %, so
+// the balls of a level cover the cell widened by 0.1 % of the piece's size, ~2.5e-4 of a cell width at depth 2.  The
+// centres are formed in fp64 (c, then +- w / 4, +- w / 8: each within 2^-51 of the grid's extent of its exact
+// place), and cut_cell assigns q to a cell from (q - lo) (1 / w) in fp64, wrong by at most a few 2^-52 of G cell
+// widths: both are below 1e-12 of a cell width for any G this library builds (G^3 < 2^32), against the 2.5e-4 to
+// spare.  Each piece takes its own guards and its own margin m = 2^-40 (|x0 - o|_1 + |pc - o|_1 + d_B + d_p) with its
+// own d_B and d_p: the same ~40 operations on operands no larger than these.  A child whose fp32 bound from c is
+// within d_p(c)^2 is tried on no piece (the caller's s0 / s1): c lies in the ball of every octant, so F(c) <= 0
+// fails the first octant it meets, at either depth.  A drop proved piece by piece is a drop proved for every q of
+// the cell, so what is said above of coarse records, flags and the alongnormal walks holds unchanged.
+//
+// The ball of one test: the expansion point relative to the tree origin, v = (x0 - pc) / d_p, d_p, the radius,
+// r2p = 2 rho^2 / d_p, and mag = |x0 - o|_1 + |pc - o|_1 + d_p.
+struct CutBall {
+    D3 xo, vp;
+    double dp, rho, r2p, mag;
+};
+// k_cut_level<*, true>'s grid argument: G below this bit (a grid has at most 2^32 cells, api.cpp build_entry_cut, so
+// G < 1626), the depth above
+constexpr int kCutSubShift = 24;
+// whether the rule proves on ball b that the child with frame ax and box [e[0..2], e[3..5]] can be dropped
+__device__ inline bool cut_ball_drops(const float (&ax)[3][3], const float (&e)[6], const CutBall& b) {
+    const double kf = 1.0 - 1e-6;
+    double g[3], d2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double p = (double)ax[k][0] * b.xo.x + (double)ax[k][1] * b.xo.y + (double)ax[k][2] * b.xo.z;
+        const double lo = (double)e[k], hi = (double)e[3 + k];
+        g[k] = p < lo ? p - lo : (p > hi ? p - hi : 0.0);
+        d2 += g[k] * g[k];
+    }
+    const double dB = sqrt(d2);
+    if (!(dB > b.rho * (1.0 + 1e-5))) return false;       // also NaN / a non-finite box
+    if (!(kf * dB - b.dp - b.r2p > 0.0)) return false;    // the common case near the foot point: no gradient needed
+    const double inv = 1.0 / dB, ks = kf * inv;
+    const D3 w = D3{ks * ((double)ax[0][0] * g[0] + (double)ax[1][0] * g[1] + (double)ax[2][0] * g[2]) - b.vp.x,
+                    ks * ((double)ax[0][1] * g[0] + (double)ax[1][1] * g[1] + (double)ax[2][1] * g[2]) - b.vp.y,
+                    ks * ((double)ax[0][2] * g[0] + (double)ax[1][2] * g[1] + (double)ax[2][2] * g[2]) - b.vp.z};
+    const double lhs = kf * dB - b.dp - b.rho * (sqrt(vdot(w, w)) + 4.0 * b.rho * inv) - b.r2p;
+    return lhs > 9.094947017729282e-13 * (b.mag + dB);  // 2^-40
+}
+// Both children at once (they share the frame); h0 / h1: in, the child passed the ball rule; out, it also survives
+// this one.  cell: the whole cell's ball (c, r).  s0 / s1: the child may be tried on sub-cells, down to depth subdiv
+// (0: the whole cell only); pco = pc - o, pmag = |pc - o|_1, qw = w / 4.  Returns whether a child was dropped.
+__device__ inline bool cut_dir_drop(const NodeV& nd, bool& h0, bool& h1, bool s0, bool s1, const CutBall& cell,
+                                    const D3& pco, double pmag, const D3& qw, int subdiv) {
     float ax[3][3], e0[6], e1[6];
     nd.frame(ax[0], ax[1], ax[2]);
     nd.extents(e0, e1);
-    double p[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) p[k] = (double)ax[k][0] * co.x + (double)ax[k][1] * co.y + (double)ax[k][2] * co.z;
-    const double kf = 1.0 - 1e-6;
     bool dropped = false;
-#pragma unroll
+    if (h0 && cut_ball_drops(ax, e0, cell)) {
+        h0 = false;
+        dropped = true;
+    }
+    if (h1 && cut_ball_drops(ax, e1, cell)) {
+        h1 = false;
+        dropped = true;
+    }
+    if (subdiv < 1) return dropped;
+    // (this kernel runs once per kept tree: one copy of the test in a loop over sides and pieces, not 2 x 16 copies)
+#pragma unroll 1
     for (int side = 0; side < 2; ++side) {
-        bool& h = side ? h1 : h0;
-        if (!h) continue;
-        const float* e = side ? e1 : e0;
-        double g[3], d2 = 0.0;
+        if (!(side ? h1 && s1 : h0 && s0)) continue;
+        float e[6];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const double lo = (double)e[k], hi = (double)e[3 + k];
-            g[k] = p[k] < lo ? p[k] - lo : (p[k] > hi ? p[k] - hi : 0.0);
-            d2 += g[k] * g[k];
+        for (int k = 0; k < 6; ++k) e[k] = side ? e1[k] : e0[k];
+        // octant o of the cell, then (sub >= 0) octant sub of that octant; the child survives at the first piece
+        // that fails at full depth
+        int o = 0, sub = -1;
+        while (o < 8) {
+            const double f1 = sub < 0 ? 0.0 : 0.5;
+            CutBall b;
+            b.xo = D3{cell.xo.x + ((o & 1) ? qw.x : -qw.x) + f1 * ((sub & 1) ? qw.x : -qw.x),
+                      cell.xo.y + ((o & 2) ? qw.y : -qw.y) + f1 * ((sub & 2) ? qw.y : -qw.y),
+                      cell.xo.z + ((o & 4) ? qw.z : -qw.z) + f1 * ((sub & 4) ? qw.z : -qw.z)};
+            b.rho = cell.rho * (sub < 0 ? 0.5 : 0.25);
+            const D3 d = vsub(b.xo, pco);
+            b.dp = sqrt(vdot(d, d));
+            bool ok = b.dp > b.rho * (1.0 + 1e-5) && b.dp < INFINITY;
+            if (ok) {
+                b.vp = D3{d.x / b.dp, d.y / b.dp, d.z / b.dp};
+                b.r2p = 2.0 * b.rho * b.rho / b.dp;
+                b.mag = fabs(b.xo.x) + fabs(b.xo.y) + fabs(b.xo.z) + pmag + b.dp;
+                ok = cut_ball_drops(ax, e, b);
+            }
+            if (sub < 0) {
+                if (ok)
+                    ++o;
+                else if (subdiv < 2)
+                    break;
+                else
+                    sub = 0;
+            } else {
+                if (!ok) break;
+                if (++sub == 8) {
+                    sub = -1;
+                    ++o;
+                }
+            }
         }
-        const double dB = sqrt(d2);
-        if (!(dB > r * (1.0 + 1e-5))) continue;       // also NaN / a non-finite box
-        if (!(kf * dB - dp - r2p > 0.0)) continue;    // the common case near the foot point: no gradient needed
-        const double inv = 1.0 / dB, ks = kf * inv;
-        const D3 w = D3{ks * ((double)ax[0][0] * g[0] + (double)ax[1][0] * g[1] + (double)ax[2][0] * g[2]) - vp.x,
-                        ks * ((double)ax[0][1] * g[0] + (double)ax[1][1] * g[1] + (double)ax[2][1] * g[2]) - vp.y,
-                        ks * ((double)ax[0][2] * g[0] + (double)ax[1][2] * g[1] + (double)ax[2][2] * g[2]) - vp.z};
-        const double lhs = kf * dB - dp - r * (sqrt(vdot(w, w)) + 4.0 * r * inv) - r2p;
-        if (lhs > 9.094947017729282e-13 * (mag + dB)) {  // 2^-40
-            h = false;
+        if (o == 8) {
+            (side ? h1 : h0) = false;
             dropped = true;
         }
     }
     return dropped;
 }
 // DIR: with the directional drop (its fp64 work doubles the kernel's registers, so the ball-rule-only launches of the
-// automatic coarse grid keep their own instantiation: C3 3.7 ms against 5.0 ms as a launch argument).
+// automatic coarse grid keep their own instantiation: C3 3.7 ms against 5.0 ms as a launch argument), proved on
+// sub-cells down to the depth that rides in the grid argument: Gs = G + (depth << kCutSubShift) for DIR, plain G
+// otherwise.  (An argument of its own would rename the ball-rule instantiations too, and a shared body inlined into
+// two kernels compiles them differently: packed, the ball-rule kernels' code is the previous round's, instruction
+// for instruction, scripts/isa_check.py --diff.)
 template <bool E4, bool DIR>
 __global__ __launch_bounds__(kBlock) void k_cut_level(const BNode* __restrict__ nodes, const TriRec* __restrict__ tris,
-                                                      double ox, double oy, double oz, double tm, int G, double lx,
+                                                      double ox, double oy, double oz, double tm, int Gs, double lx,
                                                       double ly, double lz, double wx, double wy, double wz,
                                                       const double* __restrict__ pts, const int* __restrict__ hint,
                                                       uint32_t* __restrict__ rec, const uint32_t* __restrict__ crec,
                                                       unsigned long long* __restrict__ nflag) {
+    const int G = DIR ? Gs & ((1 << kCutSubShift) - 1) : Gs;
+    const int subdiv = DIR ? Gs >> kCutSubShift : 0;
     constexpr int kw = E4 ? 8 : 16;  // record words
     // a wave takes a 4 x 4 x 4 brick of cells (bricks in row order): its cells' start lists share their nodes, and
     // under a half-resolution grid it reads 8 records
@@ -2261,9 +2348,11 @@ __global__ __launch_bounds__(kBlock) void k_cut_level(const BNode* __restrict__ 
     const D3 co = D3{c.x - ox, c.y - oy, c.z - oz};
     const bool dir = DIR && dp > r * (1.0 + 1e-5) && dp < INFINITY;
     const float dp2f = __double2float_rd(dp * dp);
-    const D3 vp = D3{(c.x - pc.x) / dp, (c.y - pc.y) / dp, (c.z - pc.z) / dp};
-    const double mag = fabs(co.x) + fabs(co.y) + fabs(co.z) + fabs(pc.x - ox) + fabs(pc.y - oy) + fabs(pc.z - oz) + dp;
-    const double r2p = 2.0 * r * r / dp;
+    const D3 pco = D3{pc.x - ox, pc.y - oy, pc.z - oz};
+    const double pmag = fabs(pco.x) + fabs(pco.y) + fabs(pco.z);
+    const CutBall ball = CutBall{co, D3{(c.x - pc.x) / dp, (c.y - pc.y) / dp, (c.z - pc.z) / dp}, dp, r, 2.0 * r * r / dp,
+                                 fabs(co.x) + fabs(co.y) + fabs(co.z) + pmag + dp};
+    const D3 qw = D3{0.25 * wx, 0.25 * wy, 0.25 * wz};  // the octants' centres: c +- w / 4
     bool flagged = false;  // a directional drop removed what the ball rule kept (here or in the coarse record)
     if (crec) {
         // start from the enclosing cell of the half-resolution grid (G = 2 Gc, the same box): a subtree its record left
@@ -2314,8 +2403,8 @@ __global__ __launch_bounds__(kBlock) void k_cut_level(const BNode* __restrict__ 
                 bd[k] = fmaxf(bd[k], fminf(d0, d1));
                 bool h0 = d0 <= limf, h1 = d1 <= limf;
                 // (a child whose fp32 bound is within d_p^2 is not tried: the rule needs d_B > d_p; skipping is safe)
-                if (dir && ((h0 && d0 > dp2f) || (h1 && d1 > dp2f)) && cut_dir_drop(nd, h0, h1, co, vp, dp, r, r2p, mag))
-                    flagged = true;
+                const bool s0 = h0 && d0 > dp2f, s1 = h1 && d1 > dp2f;
+                if (dir && (s0 || s1) && cut_dir_drop(nd, h0, h1, s0, s1, ball, pco, pmag, qw, subdiv)) flagged = true;
                 const int cnt = (int)h0 + (int)h1;
                 if (m - 1 + cnt > kCutK) {
                     stuck[k] = m;
@@ -2471,20 +2560,25 @@ int cut_centres(int G, const double* lo, const double* w, double* d_q, hipStream
 
 int cut_level(const msh_tree* tree, int G, const double* lo, const double* w, const double* d_pts, const int* d_hint,
               uint32_t* d_rec, bool e4, hipStream_t s, const uint32_t* d_half, unsigned long long* d_nflag,
-              bool directional) {
+              int subdiv) {
     const size_t GB = ((size_t)G + 3) / 4;  // 4^3-cell bricks, one per wave
     const unsigned nb = (unsigned)((GB * GB * GB * 64 + kBlock - 1) / kBlock);
     const TriRec* tris = static_cast<const TriRec*>(tree->d_leaves);
     const double tm = tree_margin(tree->half_diag);
     TimedLaunch tl("cut_level", s);
-    auto launch = [&](auto kern) {
-        kern<<<nb, kBlock, 0, s>>>(tree->d_nodes, tris, tree->origin[0], tree->origin[1], tree->origin[2], tm, G, lo[0], lo[1],
-                                   lo[2], w[0], w[1], w[2], d_pts, d_hint, d_rec, d_half, d_nflag);
+    auto launch = [&](auto kern, int Gs) {
+        kern<<<nb, kBlock, 0, s>>>(tree->d_nodes, tris, tree->origin[0], tree->origin[1], tree->origin[2], tm, Gs, lo[0],
+                                   lo[1], lo[2], w[0], w[1], w[2], d_pts, d_hint, d_rec, d_half, d_nflag);
     };
-    if (directional)
-        e4 ? launch(k_cut_level<true, true>) : launch(k_cut_level<false, true>);
-    else
-        e4 ? launch(k_cut_level<true, false>) : launch(k_cut_level<false, false>);
+    if (subdiv >= 0) {
+        // test hook: the sub-cell depth of the directional drop, 0 (the whole cell only) to kCutSubdiv
+        const char* e = getenv("MESH_AMD_CUT_SUBDIV");
+        const int depth = std::max(0, std::min(e ? atoi(e) : subdiv, kCutSubdiv));
+        const int Gs = G + (depth << kCutSubShift);
+        e4 ? launch(k_cut_level<true, true>, Gs) : launch(k_cut_level<false, true>, Gs);
+    } else {
+        e4 ? launch(k_cut_level<true, false>, G) : launch(k_cut_level<false, false>, G);
+    }
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }

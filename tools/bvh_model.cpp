@@ -777,12 +777,40 @@ bool dir_drop(const double* c, const double* pc, double r, const OBB& o) {
     for (int k = 0; k < 3; ++k) du += (g[k] / dB - e[k] / dp) * (g[k] / dB - e[k] / dp);
     return dB - dp - r * (std::sqrt(du) + 4 * r / dB + 2 * r / dp) > 1e-9 * (dB + dp);
 }
+// dir_drop as nearest.hip cut_dir_drop applies it with sub-cells: the whole cell (centre c, radius r, half-widths hw)
+// first; on failure each of its 8 octants (centres c +- hw / 2, radius r / 2) must prove the drop, with the same pc,
+// and an octant that fails is split once more (radius r / 4) when subdiv is 2.  subdiv 0: the whole cell only.
+// evals (nullable): += the rule evaluations spent.
+bool dir_drop_sub(const double* c, const double* pc, double r, const double* hw, const OBB& o, int subdiv,
+                  uint32_t* evals) {
+    if (evals) ++*evals;
+    if (dir_drop(c, pc, r, o)) return true;
+    if (subdiv < 1) return false;
+    // the kernel's prefilter: F(c) <= 0 can pass in no piece, since c lies in every octant's ball
+    const double e[3] = {c[0] - pc[0], c[1] - pc[1], c[2] - pc[2]};
+    if (!(obb_d2(c, o) > e[0] * e[0] + e[1] * e[1] + e[2] * e[2])) return false;
+    for (int a = 0; a < 8; ++a) {
+        double x1[3];
+        for (int k = 0; k < 3; ++k) x1[k] = c[k] + ((a >> k) & 1 ? 0.5 : -0.5) * hw[k];
+        if (evals) ++*evals;
+        if (dir_drop(x1, pc, 0.5 * r, o)) continue;
+        if (subdiv < 2) return false;
+        for (int b = 0; b < 8; ++b) {
+            double x2[3];
+            for (int k = 0; k < 3; ++k) x2[k] = x1[k] + ((b >> k) & 1 ? 0.25 : -0.25) * hw[k];
+            if (evals) ++*evals;
+            if (!dir_drop(x2, pc, 0.25 * r, o)) return false;
+        }
+    }
+    return true;
+}
 // start list of a cell as k_cut_level forms it: entries (nodes, or ~leaves, which are final) are replaced by their
 // children within lim of c in passes over the list while it keeps at most K entries; an entry that cannot be expanded
-// is retried once the list has shrunk.  pc (nullable): also drop the children dir_drop proves useless for the cell.
-// stuck_out: 1 when the expansion ended with an internal entry that did not fit.
+// is retried once the list has shrunk.  pc (nullable): also drop the children dir_drop_sub proves useless for the
+// cell (hw: the cell's half-widths; subdiv: the sub-cell depth).  stuck_out: 1 when the expansion ended with an
+// internal entry that did not fit.  evals_out (nullable): the directional rule's evaluations.
 std::vector<int> cell_cut_list(const ObbTree& t, const double* c, double lim, int K, const double* pc, double r,
-                               int* stuck_out) {
+                               const double* hw, int subdiv, int* stuck_out, uint32_t* evals_out) {
     std::vector<int> ref{0}, stuck{0};
     for (int pass = 0; pass < 256; ++pass) {
         bool changed = false;
@@ -794,7 +822,8 @@ std::vector<int> cell_cut_list(const ObbTree& t, const double* c, double lim, in
             const int x = ref[k];
             bool h[2];
             for (int s = 0; s < 2; ++s)
-                h[s] = obb_d2(c, t.ob[2 * x + s]) <= lim && !(pc && dir_drop(c, pc, r, t.ob[2 * x + s]));
+                h[s] = obb_d2(c, t.ob[2 * x + s]) <= lim &&
+                       !(pc && dir_drop_sub(c, pc, r, hw, t.ob[2 * x + s], subdiv, evals_out));
             const int cnt = (int)h[0] + (int)h[1];
             if (m - 1 + cnt > K) { stuck[k] = m; continue; }
             changed = true;
@@ -882,18 +911,20 @@ extern "C" void model_entry_cut(const double* v, const uint32_t* f, int T, const
 }
 
 // The start lists of k_cut_level on a G^3 grid over [blo, bhi] (at most K entries per cell, expansion in passes), with
-// the ball rule alone (rule 0) or with the directional drop as well (rule 1).  Per query inside the grid: nodes loaded
-// and leaf tests of the walk from its cell's list with a near-perfect initial bound (d* (1 + 1e-9)), the list's size,
-// and whether the expansion ended stuck on the cap.  Queries outside the grid get the walk from the root.
+// the ball rule alone (rule 0) or with the directional drop as well (rule 1; subdiv: its sub-cell depth, 0 the whole
+// cell only, dir_drop_sub).  Per query inside the grid: nodes loaded and leaf tests of the walk from its cell's list
+// with a near-perfect initial bound (d* (1 + 1e-9)), the list's size, whether the expansion ended stuck on the cap,
+// and the directional rule's evaluations while the list was formed (the build's cost).  Queries outside the grid get
+// the walk from the root.
 extern "C" void model_cut_rule(const double* v, const uint32_t* f, int T, const double* q, long S, const double* blo,
-                               const double* bhi, int G, int K, int rule, uint32_t* cut_nodes, uint32_t* cut_leaves,
-                               uint32_t* cut_size, uint32_t* cut_stuck) {
+                               const double* bhi, int G, int K, int rule, int subdiv, uint32_t* cut_nodes,
+                               uint32_t* cut_leaves, uint32_t* cut_size, uint32_t* cut_stuck, uint32_t* cut_evals) {
     ObbTree t = make_obb_tree(v, f, T);
 #pragma omp parallel for schedule(dynamic, 64)
     for (long i = 0; i < S; ++i) {
         const double* qq = q + 3 * i;
         const double d2 = exact_d2(t, v, f, qq);
-        double c[3], r2 = 0;
+        double c[3], hw[3], r2 = 0;
         bool inside = true;
         for (int k = 0; k < 3; ++k) {
             const double w = (bhi[k] - blo[k]) / G;
@@ -901,12 +932,13 @@ extern "C" void model_cut_rule(const double* v, const uint32_t* f, int T, const 
             if (ci < 0 || ci >= G) inside = false;
             ci = std::min(std::max(ci, 0), G - 1);
             c[k] = blo[k] + (ci + 0.5) * w;
+            hw[k] = 0.5 * w;
             r2 += 0.25 * w * w;
         }
-        uint32_t cn = 0, cl = 0;
+        uint32_t cn = 0, cl = 0, ev = 0;
         if (!inside) {
             walk(t, v, f, qq, std::vector<int>{0}, d2 * (1 + 1e-9), cn, cl, nullptr);
-            cut_nodes[i] = cn; cut_leaves[i] = cl; cut_size[i] = 0; cut_stuck[i] = 0;
+            cut_nodes[i] = cn; cut_leaves[i] = cl; cut_size[i] = 0; cut_stuck[i] = 0; cut_evals[i] = 0;
             continue;
         }
         const double r = std::sqrt(r2) * 1.001;
@@ -921,9 +953,10 @@ extern "C" void model_cut_rule(const double* v, const uint32_t* f, int T, const 
         const double dc = std::sqrt(dc2);
         const double lim = (dc + 2 * r) * (dc + 2 * r) * (1 + 1e-9);
         int st = 0;
-        std::vector<int> cut = cell_cut_list(t, c, lim, K, rule ? pc : nullptr, r, &st);
+        std::vector<int> cut = cell_cut_list(t, c, lim, K, rule ? pc : nullptr, r, hw, subdiv, &st, &ev);
         walk_from(t, v, f, qq, cut, d2 * (1 + 1e-9), cn, cl);
         cut_nodes[i] = cn; cut_leaves[i] = cl; cut_size[i] = (uint32_t)cut.size(); cut_stuck[i] = (uint32_t)st;
+        cut_evals[i] = ev;
     }
 }
 
