@@ -249,6 +249,39 @@ int msh_visibility_stats(msh_tree* tree, const double* d_cams, size_t C, double 
 int msh_tree_intersections(msh_tree* tree, const double* qv, size_t Pq, const uint32_t* qf, size_t Tq, uint32_t* out,
                            size_t* K);
 
+/* ---- intersection pair lists (no reference counterpart: the reference stops at the first hit) ----
+ * Which face hits which face, for collision and interpenetration terms, contact detection and mesh repair.
+ * Query mode: all (i, j) for which query face i of (qv, qf) and the tree's leaf primitive j overlap, by the closed
+ * predicate msh_tree_intersections uses (touching counts, coplanar pairs included), called as overlap(query_i, mesh_j).
+ * j is the face id of the leaf: on a tree built with extra faces (msh_tree_build_ex) it ranges over the main faces
+ * [0, T) and the extra faces [T, T + ET), as msh_tree_intersections tests them all.  Plain triangle trees (kind 0).
+ * Self mode: all (i, j), i < j, both faces of the tree, that overlap (overlap(tri_i, tri_j)) and share no exactly
+ * equal vertex coordinate -- the rule of msh_ntree_selfintersects; plain and normals-metric trees (kinds 0, 1); a tree
+ * built with extra faces is MSH_EINVAL.
+ * pairs is (K, 2) u32 row-major, sorted ascending by (i, j), without duplicates.  counts (optional, may be NULL) gets
+ * one u32 per row -- Tq rows in query mode, T in self mode, rows being face ids, not leaf positions --: the number of
+ * pairs whose first member is that row, so an exclusive scan of it indexes pairs as CSR.  The same inputs give the
+ * same bytes on every call (no atomics decide order or content).
+ * cap protocol: *K always receives the full pair count; the first min(K, cap) pairs in sorted order are written to
+ * pairs (capacity cap pairs = 2 cap u32).  cap == 0 with pairs == NULL counts only: nothing is filled or sorted.
+ * Tq == 0: K = 0.  K is limited to 2^32 - 1 (MSH_EINVAL beyond, found by a 64-bit sum of the counts), Tq to 2^31 - 1.
+ * Point trees, batched trees and NULL handles are MSH_EINVAL.  The host entry points check every query face index
+ * (MSH_EINVAL); the device ones detect an index >= Pq on the device (MSH_EINVAL, nothing is read out of bounds, the
+ * handle stays usable).
+ * The *_device entry points take device pointers and are synchronous up to the moment K is known (one 24-byte
+ * read-back on `stream` after the counting pass); the scan, fill and order launches after it, and the copy into
+ * d_counts, are asynchronous on `stream`.  The calls stay on the handle's own device (no row split over replicas).
+ * msh_timing_get names: "tritri_count" (the counting traversal), "tritri_scan" (the totals, then the offsets),
+ * "tritri_fill" (the second traversal; it also orders rows of up to 32 hits) and "tritri_order" (only when a row is
+ * longer: two stable radix sorts of all pairs and the interleave). */
+int msh_tree_intersection_pairs(msh_tree* tree, const double* qv, size_t Pq, const uint32_t* qf, size_t Tq,
+                                uint32_t* pairs, size_t cap, uint32_t* counts, size_t* K);
+int msh_tree_intersection_pairs_device(msh_tree* tree, const double* d_qv, size_t Pq, const uint32_t* d_qf, size_t Tq,
+                                       uint32_t* d_pairs, size_t cap, uint32_t* d_counts, size_t* K, void* stream);
+int msh_tree_self_intersection_pairs(msh_tree* tree, uint32_t* pairs, size_t cap, uint32_t* counts, size_t* K);
+int msh_tree_self_intersection_pairs_device(msh_tree* tree, uint32_t* d_pairs, size_t cap, uint32_t* d_counts,
+                                            size_t* K, void* stream);
+
 /* ---- aabb_normals (aabb_normals.cpp, AABB_n_tree.h) ---- */
 /* aabbtree_n_compute(v, f, eps): aabb_normals.cpp:63-110 */
 int msh_ntree_build(const double* v, size_t P, const uint32_t* f, size_t T, double eps, msh_tree** out);

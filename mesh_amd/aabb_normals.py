@@ -51,3 +51,13 @@ def aabbtree_n_selfintersects(tree):
     c = N.ctypes.c_int64(0)
     N.check(N.lib().msh_ntree_selfintersects(tree.ptr, N.ctypes.byref(c)))
     return int(c.value)
+
+
+def aabbtree_n_selfintersections_pairs(tree, return_counts=False):
+    """The pairs behind ``aabbtree_n_selfintersects``: all (i, j), i < j, of faces that intersect and share no exactly
+    equal vertex coordinate, (K, 2) uint32 sorted by (i, j) -- ``np.unique(pairs).size`` is that function's count --
+    and with ``return_counts`` the (T,) uint32 number of pairs whose smaller face is each face.  No reference
+    counterpart."""
+    from . import spatialsearch
+    tree = spatialsearch._pairs_tree(tree, "aabbtree_n_selfintersections_pairs", ("normals",))
+    return spatialsearch._self_pairs(tree, return_counts)

@@ -2290,6 +2290,136 @@ int msh_tree_intersections(msh_tree* t, const double* qv, size_t Pq, const uint3
     return MSH_OK;
 }
 
+// ---- intersection pair lists (tritri.hip k_tritri_all) ----
+static int check_pairs_tree(const msh_tree* t, bool self, const char* fn) {
+    MSH_TRY(check_tree(t, kTriangles, fn));
+    if (!self && t->kind != kTriangles) {
+        set_error("%s: wrong handle kind %d (a plain triangle tree is needed)", fn, t->kind);
+        return MSH_EINVAL;
+    }
+    if (self && t->T != t->T_main) {
+        set_error("%s: the tree was built with %zu extra faces (self mode needs the main mesh alone)", fn,
+                  t->T - t->T_main);
+        return MSH_EINVAL;
+    }
+    return MSH_OK;
+}
+
+static int check_pairs_args(const uint32_t* pairs, size_t cap, size_t* K, size_t rows, const char* fn) {
+    if (!K || (cap && !pairs)) {
+        set_error("%s: null argument", fn);
+        return MSH_EINVAL;
+    }
+    *K = 0;
+    // rows index the packed triangle records as int on the device
+    if (rows > (size_t)0x7FFFFFFFull) {
+        set_error("%s: %zu query faces exceed the 31-bit index range of one call (split the query mesh)", fn, rows);
+        return MSH_EINVAL;
+    }
+    return MSH_OK;
+}
+
+// Count, read K back, then scan / fill / order the first min(K, cap) pairs (launch_tri_pairs_*).  host_out: pairs and
+// counts are host arrays -- the pairs come through a device buffer of their own and the call returns after the
+// download; otherwise they are device arrays and everything after the read-back of K is left queued on s.
+static int pairs_run(msh_tree* t, const TriRec* d_q, size_t rows, int self_mode, bool packed, bool host_out,
+                     uint32_t* pairs, size_t cap, uint32_t* counts, size_t* K, hipStream_t s, const char* fn) {
+    DevBuf dp;
+    int st = MSH_OK;
+    do {
+        WsOrder order(t, s);
+        PairTotals tot{};
+        if ((st = launch_tri_pairs_count(t, d_q, rows, self_mode, packed, &tot, s)) != MSH_OK) break;
+        const uint64_t k = tot.K;
+        if (tot.bad_face) {
+            set_error("%s: query face index out of range (>= the number of query vertices)", fn);
+            st = MSH_EINVAL;
+            break;
+        }
+        // the 64-bit sum is the detector: the 32-bit scan below is never run on counts it would wrap on
+        if (k > 0xFFFFFFFFull) {
+            set_error("%s: %llu pairs exceed the 32-bit offset range of one call (split the query mesh)", fn,
+                      (unsigned long long)k);
+            st = MSH_EINVAL;
+            break;
+        }
+        *K = (size_t)k;
+        const size_t n = std::min<size_t>((size_t)k, cap);
+        uint32_t* d_pairs = pairs;
+        if (host_out && n) {
+            if ((st = dp.reserve(2 * n * sizeof(uint32_t))) != MSH_OK) break;
+            d_pairs = dp.as<uint32_t>();
+        }
+        if ((st = launch_tri_pairs_emit(t, d_q, rows, self_mode, tot, d_pairs, n, s)) != MSH_OK) break;
+        hipError_t e = hipSuccess;
+        const hipMemcpyKind kind = host_out ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        if (counts) e = hipMemcpyAsync(counts, t->ws.flags.ptr, rows * sizeof(uint32_t), kind, s);
+        if (e == hipSuccess && host_out && n)
+            e = hipMemcpyAsync(pairs, d_pairs, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && host_out) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            set_error("%s: %s", fn, hipGetErrorString(e));
+            st = MSH_EDEVICE;
+        }
+    } while (0);
+    if (host_out || st != MSH_OK) (void)hipStreamSynchronize(s);
+    dp.release();
+    return st;
+}
+
+int msh_tree_intersection_pairs(msh_tree* t, const double* qv, size_t Pq, const uint32_t* qf, size_t Tq, uint32_t* pairs,
+                                size_t cap, uint32_t* counts, size_t* K) {
+    const char* fn = "msh_tree_intersection_pairs";
+    MSH_TRY(check_pairs_tree(t, false, fn));
+    MSH_TRY(check_pairs_args(pairs, cap, K, Tq, fn));
+    if (Tq == 0) return MSH_OK;
+    if (!qv || !qf) { set_error("%s: null argument", fn); return MSH_EINVAL; }
+    MSH_TRY(check_faces(qf, Tq, Pq, "query faces"));
+    hipStream_t s = t->stream;
+    std::vector<TriRec> ht;
+    host_tris(qv, qf, Tq, ht);
+    DevBuf dq;
+    int st = upload(dq, ht.data(), Tq, s);
+    if (st == MSH_OK) st = pairs_run(t, dq.as<TriRec>(), Tq, 0, false, true, pairs, cap, counts, K, s, fn);
+    (void)hipStreamSynchronize(s);
+    dq.release();
+    return st;
+}
+
+int msh_tree_intersection_pairs_device(msh_tree* t, const double* d_qv, size_t Pq, const uint32_t* d_qf, size_t Tq,
+                                       uint32_t* d_pairs, size_t cap, uint32_t* d_counts, size_t* K, void* stream) {
+    const char* fn = "msh_tree_intersection_pairs_device";
+    MSH_TRY(check_pairs_tree(t, false, fn));
+    MSH_TRY(check_pairs_args(d_pairs, cap, K, Tq, fn));
+    if (Tq == 0) return MSH_OK;
+    if (!d_qv || !d_qf) { set_error("%s: null argument", fn); return MSH_EINVAL; }
+    hipStream_t s = pick(t, stream);
+    {
+        // the packed triangles live in the workspace too: order them after the handle's previous call (pairs_run's
+        // own WsOrder then waits for an event this stream has already passed)
+        WsOrder order(t, s);
+        MSH_TRY(pack_query_tris(t, d_qv, Pq, d_qf, Tq, s));
+    }
+    return pairs_run(t, t->ws.q.as<TriRec>(), Tq, 0, true, false, d_pairs, cap, d_counts, K, s, fn);
+}
+
+int msh_tree_self_intersection_pairs(msh_tree* t, uint32_t* pairs, size_t cap, uint32_t* counts, size_t* K) {
+    const char* fn = "msh_tree_self_intersection_pairs";
+    MSH_TRY(check_pairs_tree(t, true, fn));
+    MSH_TRY(check_pairs_args(pairs, cap, K, t->T, fn));
+    return pairs_run(t, static_cast<const TriRec*>(t->d_leaves), t->T, 1, false, true, pairs, cap, counts, K, t->stream,
+                     fn);
+}
+
+int msh_tree_self_intersection_pairs_device(msh_tree* t, uint32_t* d_pairs, size_t cap, uint32_t* d_counts, size_t* K,
+                                            void* stream) {
+    const char* fn = "msh_tree_self_intersection_pairs_device";
+    MSH_TRY(check_pairs_tree(t, true, fn));
+    MSH_TRY(check_pairs_args(d_pairs, cap, K, t->T, fn));
+    return pairs_run(t, static_cast<const TriRec*>(t->d_leaves), t->T, 1, false, false, d_pairs, cap, d_counts, K,
+                     pick(t, stream), fn);
+}
+
 int msh_ntree_nearest(msh_tree* t, const double* q, const double* n, size_t S, uint32_t* face, double* pt) {
     MSH_TRY(check_tree(t, kNormals, "msh_ntree_nearest"));
     MSH_TRY(check_count(S, "msh_ntree_nearest"));

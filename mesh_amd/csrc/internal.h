@@ -303,6 +303,25 @@ int launch_visibility_stats(const msh_tree* tree, const double* d_cams, size_t C
 // the query triangles are the tree's own leaves in face order).
 int launch_tri_intersect(const msh_tree* tree, const TriRec* d_qtris, size_t Tq, int self_mode, uint32_t* d_flags,
                          hipStream_t s);
+// All hits as a pair list (row, mesh face), sorted by (row, mesh face).  A row is the query triangle's index, or in self
+// mode (d_qtris = the tree's leaves, Tq = T) its face id, with only pairs row < mesh face kept.  Two steps, both using
+// tree->ws (flags: the per-row counts, which stay valid between them; counters, ranges, the four sort buffers, spill):
+//   count  the per-row counts and their totals, read back on s (synchronous).  packed: pack_query_tris ran before
+//          on s, and bad_face says whether it met a face index >= Pq;
+//   emit   scan, fill, order: the first n_emit <= K pairs to d_pairs (n_emit, 2); asynchronous on s.  K <= 2^32 - 1.
+//          When no row is longer than tritri.hip's kLaneSort the fill lanes order their own rows and write the pairs;
+//          otherwise all K pairs go through two stable radix sorts (mesh face, then row).
+struct PairTotals {
+    uint64_t K;        // 64-bit sum of the counts
+    uint64_t longest;  // the largest count
+    bool bad_face;
+};
+int launch_tri_pairs_count(msh_tree* tree, const TriRec* d_qtris, size_t Tq, int self_mode, bool packed, PairTotals* out,
+                           hipStream_t s);
+int launch_tri_pairs_emit(msh_tree* tree, const TriRec* d_qtris, size_t Tq, int self_mode, const PairTotals& tot,
+                          uint32_t* d_pairs, size_t n_emit, hipStream_t s);
+// query triangles of device arrays qv (Pq,3), qf (Tq,3) into tree->ws.q (TriRec, face = row)
+int pack_query_tris(msh_tree* tree, const double* d_qv, size_t Pq, const uint32_t* d_qf, size_t Tq, hipStream_t s);
 
 // ---- mesh geometry (geometry.hip) ----
 // area-weighted vertex normals of (P,3) v over (T,3) f: sum of the faces' cross products in ascending

@@ -3,6 +3,8 @@
 //     one lane per query-mesh triangle, flag = 1 iff it touches any mesh triangle (closed test).
 //   * aabbtree_n_selfintersects (aabb_normals.cpp:192-207, AABB_n_tree.h:107-116): one lane per mesh
 //     triangle, pairs sharing an exactly equal vertex coordinate are skipped.
+// K6b -- the same traversal without the early exit, for the pair lists (msh_tree_intersection_pairs,
+// msh_tree_self_intersection_pairs; no reference counterpart): k_tritri_all and its launchers at the end of the file.
 // The overlap test is the orientation-predicate test of Guigue & Devillers (2003) evaluated in fp64,
 // with a 2-D edge/containment test for the coplanar case.  Boxes: closed fp64 separating-axis test of
 // the triangle against each child's outward-rounded oriented box, on the node frame's three axes.
@@ -241,6 +243,303 @@ int launch_tri_intersect(const msh_tree* tree, const TriRec* d_qtris, size_t Tq,
     }
     TimedLaunch tl("tritri", s);
     k_tritri<<<nblk, kBlock, 0, s>>>(a);
+    MSH_HIP(hipGetLastError());
+    return MSH_OK;
+}
+
+// ---- all hits: the (query face, mesh face) pair list ----
+// Count, sum, scan, fill, order (DESIGN.md "Intersection pair lists").  k_tritri_all is k_tritri's traversal without
+// the early exit, run twice with the same body: kFill == false counts the hits of every row, kFill == true writes
+// them at the row's offset.  A row is the query triangle's index (query mode) or its face id (self mode: the queries
+// are the tree's own leaves, in leaf order; only leaves of a larger face id are kept, so every pair appears once, under
+// its smaller face, and the predicate gets the smaller face first).  Nothing but a row's own lane writes its count
+// or its segment, so the output does not depend on how lanes are scheduled.
+constexpr int kLaneSort = 32;  // rows of up to this many hits are ordered by their own lane (k_tritri_all)
+
+struct PairArgs {
+    const BNode* nodes;
+    const TriRec* tris;
+    size_t T;
+    const TriRec* q;
+    size_t Tq;
+    int self_mode;
+    uint32_t* counts;         // per row; written by the count pass, read by the fill pass
+    const uint32_t* offsets;  // exclusive scan of counts (fill pass)
+    uint32_t* ids;            // fill pass: mesh face of pair offsets[row] + k ...
+    uint32_t* rows;           // ... and its row (nullptr when the lanes order their own rows)
+    uint32_t* pairs;          // fill pass, every row <= kLaneSort hits: the output (n_emit, 2); else nullptr
+    size_t n_emit;
+    uint2* spill;
+    int spill_depth;
+    double org[3];  // tree origin
+};
+
+// waves_per_eu(3): k_tritri's occupancy (162 VGPRs); without the hint the fill pass took 169, one over the step to 2 waves
+template <bool kFill>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) void k_tritri_all(PairArgs a) {
+    __shared__ uint2 stk[kStack * kBlock];
+    const int tid = threadIdx.x;
+    uint2* lds = stk + tid;
+    for (size_t i = (size_t)blockIdx.x * kBlock + tid; i < a.Tq; i += (size_t)gridDim.x * kBlock) {
+        uint2* spill = a.spill ? a.spill + (size_t)blockIdx.x * kBlock * (size_t)a.spill_depth + tid : nullptr;
+        D3 qa, qb, qc;
+        uint32_t qface;
+        load_tri(a.q, (int)i, qa, qb, qc, qface);
+        const uint32_t row = a.self_mode ? qface : (uint32_t)i;
+        // fill pass: this row's segment is [base, base + lim); a row without hits has nothing to walk for, and a walk
+        // ends with its last hit (the count pass made the same walk to the end and found lim of them)
+        uint32_t base = 0;
+        uint32_t lim = 0;
+        if (kFill) {
+            base = a.offsets[row];
+            lim = a.counts[row];
+            if (lim == 0) continue;
+        }
+        const D3 org = D3{a.org[0], a.org[1], a.org[2]};
+        const D3 ra = vsub(qa, org), rb = vsub(qb, org), rc = vsub(qc, org);
+        uint32_t n = 0;
+        auto leaf_test = [&](int leaf) {
+            D3 a0, a1, a2;
+            uint32_t f;
+            load_tri(a.tris, leaf, a0, a1, a2, f);
+            if (a.self_mode) {
+                if (f <= qface) return;
+                if (veq(qa, a0) || veq(qa, a1) || veq(qa, a2) || veq(qb, a0) || veq(qb, a1) || veq(qb, a2) ||
+                    veq(qc, a0) || veq(qc, a1) || veq(qc, a2))
+                    return;
+            }
+            if (!tri_tri_overlap(qa, qb, qc, a0, a1, a2)) return;
+            if (kFill && n < lim) {  // never at or beyond the segment's end, whatever the walk meets
+                a.ids[(size_t)base + n] = f;
+                if (a.rows) a.rows[(size_t)base + n] = row;
+            }
+            ++n;
+        };
+        if (a.T == 1) {
+            leaf_test(0);
+        } else {
+            int node = 0, sp = 0;
+            for (size_t guard = 0; guard < a.T; ++guard) {
+                const NodeV nd = load_node(a.nodes, node);
+                float e0[6], e1[6];
+                nd.extents(e0, e1);
+                const TriProj tp = tri_proj(frame_d(nd), ra, rb, rc);
+                bool h0 = obb_overlap(tp, e0);
+                bool h1 = obb_overlap(tp, e1);
+                const int c0 = nd.child(0), c1 = nd.child(1);
+                if (h0 && c0 < 0) { leaf_test(~c0); h0 = false; }
+                if (h1 && c1 < 0) { leaf_test(~c1); h1 = false; }
+                if (kFill && n >= lim) break;
+                if (h0 && h1) {
+                    const uint2 e = make_uint2((unsigned)c1, 0u);
+                    stack_put(lds, spill, sp, e);
+                    ++sp;
+                    node = c0;
+                    continue;
+                }
+                if (h0) { node = c0; continue; }
+                if (h1) { node = c1; continue; }
+                if (sp == 0) break;
+                --sp;
+                node = (int)stack_get(lds, spill, sp).x;
+            }
+        }
+        if (!kFill) a.counts[row] = n;
+        // Short rows are ordered by their own lane: the face ids of a row are distinct, so pair k of the row is the
+        // smallest id above pair k - 1's -- lim^2 reads of the segment the lane has just written, lim <= kLaneSort.
+        if (kFill && a.pairs) {
+            uint32_t last = 0;
+            for (uint32_t k = 0; k < lim && (size_t)base + k < a.n_emit; ++k) {
+                uint32_t best = 0xFFFFFFFFu;  // not a face id (ids < 2^31)
+                for (uint32_t m = 0; m < lim; ++m) {
+                    const uint32_t f = a.ids[(size_t)base + m];
+                    if ((k == 0 || f > last) && f < best) best = f;
+                }
+                a.pairs[2 * ((size_t)base + k)] = row;
+                a.pairs[2 * ((size_t)base + k) + 1] = best;
+                last = best;
+            }
+        }
+    }
+}
+
+// out[0] += the 64-bit sum of counts, out[1] = max(out[1], the largest count) (out zeroed by the caller; an integer sum
+// and a maximum, so the order of the blocks' atomic operations does not show in them)
+__global__ __launch_bounds__(kBlock) void k_sum_counts(const uint32_t* __restrict__ counts, size_t n,
+                                                       unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long sh[kBlock], shm[kBlock];
+    unsigned long long acc = 0, mx = 0;
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
+        const unsigned long long c = counts[i];
+        acc += c;
+        mx = c > mx ? c : mx;
+    }
+    sh[threadIdx.x] = acc;
+    shm[threadIdx.x] = mx;
+    __syncthreads();
+    for (int o = kBlock / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            sh[threadIdx.x] += sh[threadIdx.x + o];
+            shm[threadIdx.x] = shm[threadIdx.x + o] > shm[threadIdx.x] ? shm[threadIdx.x + o] : shm[threadIdx.x];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && sh[0]) {
+        atomicAdd(out, sh[0]);
+        atomicMax(out + 1, shm[0]);
+    }
+}
+
+// pairs (n, 2) row-major from the sorted (row, mesh face) columns
+__global__ __launch_bounds__(kBlock) void k_emit_pairs(const uint32_t* __restrict__ rows, const uint32_t* __restrict__ ids,
+                                                       size_t n, uint32_t* __restrict__ pairs) {
+    const size_t p = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n) return;
+    pairs[2 * p] = rows[p];
+    pairs[2 * p + 1] = ids[p];
+}
+
+// query triangles from device arrays, in the manner of k_pack_tris; a face with an index >= Pq becomes a zero
+// triangle and sets *err (no read outside qv)
+__global__ __launch_bounds__(kBlock) void k_pack_query_tris(const double* __restrict__ qv, size_t Pq,
+                                                            const uint32_t* __restrict__ qf, size_t Tq,
+                                                            TriRec* __restrict__ out, unsigned long long* __restrict__ err) {
+    const size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= Tq) return;
+    const size_t i0 = qf[3 * t], i1 = qf[3 * t + 1], i2 = qf[3 * t + 2];
+    const bool ok = i0 < Pq && i1 < Pq && i2 < Pq;
+    const size_t vi[3] = {i0, i1, i2};
+    TriRec r;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) r.v[3 * c + k] = ok ? qv[3 * vi[c] + k] : 0.0;
+    r.face = (uint32_t)t;
+    r.pad = 0;
+    out[t] = r;
+    if (!ok) atomicOr(err, 1ull);
+}
+
+static unsigned pair_blocks(const msh_tree* tree, size_t n) {
+    int cu = 0;
+    if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, tree->device) != hipSuccess || cu <= 0) cu = 256;
+    return (unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, (size_t)cu * 5);
+}
+
+// the traversal's arguments and, for a tree deeper than kStack, its spill area, sized as launch_tri_intersect does
+static int pair_args(msh_tree* t, const TriRec* d_qtris, size_t Tq, int self_mode, unsigned nblk, PairArgs* out) {
+    PairArgs a{};
+    a.nodes = t->d_nodes;
+    a.tris = static_cast<const TriRec*>(t->d_leaves);
+    a.T = t->T;
+    a.q = d_qtris;
+    a.Tq = Tq;
+    a.self_mode = self_mode;
+    for (int k = 0; k < 3; ++k) a.org[k] = t->origin[k];
+    a.counts = t->ws.flags.as<uint32_t>();
+    if (t->max_depth + 1 > kStack) {
+        a.spill_depth = t->max_depth + 1 - kStack + 1;
+        MSH_TRY(t->ws.spill.reserve((size_t)nblk * kBlock * (size_t)a.spill_depth * sizeof(uint2)));
+        a.spill = t->ws.spill.as<uint2>();
+    }
+    *out = a;
+    return MSH_OK;
+}
+
+// ws.counters of a pair-list call: [0] the 64-bit sum of the counts, [1] the largest count, [2] set by
+// k_pack_query_tris when a query face index is out of range
+constexpr int kPairWords = 3;
+
+int pack_query_tris(msh_tree* tree, const double* d_qv, size_t Pq, const uint32_t* d_qf, size_t Tq, hipStream_t s) {
+    Workspace& ws = tree->ws;
+    MSH_TRY(ws.q.reserve(Tq * sizeof(TriRec)));
+    MSH_TRY(ws.counters.reserve(kPairWords * sizeof(unsigned long long)));
+    MSH_HIP(hipMemsetAsync(ws.counters.ptr, 0, kPairWords * sizeof(unsigned long long), s));
+    k_pack_query_tris<<<(unsigned)((Tq + kBlock - 1) / kBlock), kBlock, 0, s>>>(
+        d_qv, Pq, d_qf, Tq, ws.q.as<TriRec>(), ws.counters.as<unsigned long long>() + 2);
+    MSH_HIP(hipGetLastError());
+    return MSH_OK;
+}
+
+int launch_tri_pairs_count(msh_tree* tree, const TriRec* d_qtris, size_t Tq, int self_mode, bool packed, PairTotals* out,
+                           hipStream_t s) {
+    Workspace& ws = tree->ws;
+    MSH_TRY(ws.flags.reserve(Tq * sizeof(uint32_t)));
+    MSH_TRY(ws.counters.reserve(kPairWords * sizeof(unsigned long long)));
+    unsigned long long* d_tot = ws.counters.as<unsigned long long>();
+    // pack_query_tris zeroed the words on this stream already, and its kernel may have set the third
+    if (!packed) MSH_HIP(hipMemsetAsync(d_tot, 0, kPairWords * sizeof(unsigned long long), s));
+    const unsigned nblk = pair_blocks(tree, Tq);
+    PairArgs a;
+    MSH_TRY(pair_args(tree, d_qtris, Tq, self_mode, nblk, &a));
+    {
+        TimedLaunch tl("tritri_count", s);
+        k_tritri_all<false><<<nblk, kBlock, 0, s>>>(a);
+        MSH_HIP(hipGetLastError());
+    }
+    {
+        TimedLaunch tl("tritri_scan", s);
+        k_sum_counts<<<std::min(nblk, 1024u), kBlock, 0, s>>>(a.counts, Tq, d_tot);
+        MSH_HIP(hipGetLastError());
+    }
+    unsigned long long h[kPairWords] = {0, 0, 0};
+    MSH_HIP(hipMemcpyAsync(h, d_tot, sizeof(h), hipMemcpyDeviceToHost, s));
+    MSH_HIP(hipStreamSynchronize(s));
+    out->K = h[0];
+    out->longest = h[1];
+    out->bad_face = h[2] != 0;
+    return MSH_OK;
+}
+
+int launch_tri_pairs_emit(msh_tree* tree, const TriRec* d_qtris, size_t Tq, int self_mode, const PairTotals& tot,
+                          uint32_t* d_pairs, size_t n_emit, hipStream_t s) {
+    const size_t K = (size_t)tot.K;
+    if (K == 0 || n_emit == 0) return MSH_OK;
+    Workspace& ws = tree->ws;
+    const bool lane_order = tot.longest <= (uint64_t)kLaneSort;
+    MSH_TRY(ws.ranges.reserve(Tq * sizeof(uint32_t)));
+    MSH_TRY(ws.keys.reserve(K * sizeof(uint32_t)));
+    if (!lane_order) {
+        MSH_TRY(ws.vals.reserve(K * sizeof(uint32_t)));
+        MSH_TRY(ws.keys_alt.reserve(K * sizeof(uint32_t)));
+        MSH_TRY(ws.vals_alt.reserve(K * sizeof(uint32_t)));
+    }
+    const unsigned nblk = pair_blocks(tree, Tq);
+    PairArgs a;
+    MSH_TRY(pair_args(tree, d_qtris, Tq, self_mode, nblk, &a));
+    uint32_t* offsets = ws.ranges.as<uint32_t>();
+    {
+        TimedLaunch tl("tritri_scan", s);
+        MSH_HIP(hipMemcpyAsync(offsets, a.counts, Tq * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        MSH_TRY(exclusive_scan_u32(offsets, Tq, ws, s));
+    }
+    a.offsets = offsets;
+    a.ids = ws.keys.as<uint32_t>();
+    a.rows = lane_order ? nullptr : ws.vals.as<uint32_t>();
+    a.pairs = lane_order ? d_pairs : nullptr;
+    a.n_emit = n_emit;
+    {
+        TimedLaunch tl("tritri_fill", s);
+        k_tritri_all<true><<<nblk, kBlock, 0, s>>>(a);
+        MSH_HIP(hipGetLastError());
+    }
+    if (lane_order) return MSH_OK;
+    // Long rows: the segments are in row order already; a stable sort of all K pairs by mesh face and then by row
+    // leaves them sorted by (row, mesh face), in time linear in K however long a row is.
+    TimedLaunch tl("tritri_order", s);
+    auto bits_of = [](size_t n) {  // bits that hold 0 .. n - 1
+        int b = 0;
+        while (n > 1 && ((size_t)1 << b) < n) ++b;
+        return b;
+    };
+    uint32_t *ids = a.ids, *rows = a.rows, *ids_alt = ws.keys_alt.as<uint32_t>(), *rows_alt = ws.vals_alt.as<uint32_t>();
+    bool alt = false;
+    MSH_TRY(radix_sort_pairs(ids, rows, ids_alt, rows_alt, K, bits_of(tree->T), ws, s, 0, &alt));
+    if (alt) { std::swap(ids, ids_alt); std::swap(rows, rows_alt); }
+    alt = false;
+    MSH_TRY(radix_sort_pairs(rows, ids, rows_alt, ids_alt, K, bits_of(Tq), ws, s, 0, &alt));
+    if (alt) { std::swap(ids, ids_alt); std::swap(rows, rows_alt); }
+    k_emit_pairs<<<(unsigned)((n_emit + kBlock - 1) / kBlock), kBlock, 0, s>>>(rows, ids, n_emit, d_pairs);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }

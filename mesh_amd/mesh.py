@@ -186,3 +186,8 @@ class Mesh(object):
     def contains(self, vertices):
         """bool (S,): whether each row of `vertices` lies inside this (closed, outward-oriented) mesh."""
         return self._tree_for_batch(vertices).contains(vertices)
+
+    def self_intersection_pairs(self):
+        """(K, 2) uint32, sorted: the pairs (i, j), i < j, of faces of this mesh that intersect and share no exactly
+        equal vertex coordinate (search.AabbTree.selfintersections_pairs on a tree built for this call)."""
+        return self.compute_aabb_tree().selfintersections_pairs()

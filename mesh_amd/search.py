@@ -102,6 +102,18 @@ class AabbTree(object):
         from . import spatialsearch
         return spatialsearch.aabbtree_intersections_indices(self.cpp_handle, _f64c(q_v), _u32c(q_f))
 
+    def intersections_pairs(self, q_v, q_f):
+        """All (query face, mesh face) pairs of the query triangles ``q_v[q_f]`` and the mesh that touch: (K, 2) u32
+        sorted by (query face, mesh face); ``intersections_indices`` is its distinct first column."""
+        from . import spatialsearch
+        return spatialsearch.aabbtree_intersections_pairs(self.cpp_handle, _f64c(q_v), _u32c(q_f))
+
+    def selfintersections_pairs(self):
+        """All pairs (i, j), i < j, of faces of the mesh that intersect and share no exactly equal vertex coordinate:
+        (K, 2) u32 sorted by (i, j)."""
+        from . import spatialsearch
+        return spatialsearch.aabbtree_selfintersections_pairs(self.cpp_handle)
+
 
 class ClosestPointTree(object):
     """Nearest mesh vertex for query points; faces are ignored (search.py:52-65)."""
@@ -175,6 +187,12 @@ class AabbNormalsTree(object):
     def nearest(self, v_samples, n_samples):
         from . import aabb_normals
         return aabb_normals.aabbtree_n_nearest(self.tree_handle, v_samples, n_samples)
+
+    def selfintersections_pairs(self):
+        """All pairs (i, j), i < j, of faces of the mesh that intersect and share no exactly equal vertex coordinate:
+        (K, 2) u32 sorted by (i, j)."""
+        from . import aabb_normals
+        return aabb_normals.aabbtree_n_selfintersections_pairs(self.tree_handle)
 
 
 class AabbTreeBatch(object):

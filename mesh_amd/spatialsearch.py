@@ -9,6 +9,8 @@ constructions).  Deliberate differences:
     uninitialised memory, :309-311); dist stays 1e100 as in the reference.
   * ``aabbtree_intersections_indices`` is registered and returns ascending indices (reference: not in
     the method table, :35-40, and racy push_back, :393-402).
+Beyond the reference: ``aabbtree_intersections_pairs`` / ``aabbtree_selfintersections_pairs`` return which face
+hits which face, as a sorted (K, 2) pair list.
 """
 import numpy as np
 
@@ -147,3 +149,72 @@ def aabbtree_intersections_indices(tree, qv, qf):
     N.check(N.lib().msh_tree_intersections(tree.ptr, N.dptr(qv), qv.shape[0], N.uptr(qf), qf.shape[0], N.uptr(out),
                                             N.ctypes.byref(K)), Mesh_IntersectionsError)
     return out[:K.value].copy()
+
+
+def _pairs_tree(tree, fn, kinds):
+    if not isinstance(tree, N.Handle) or tree.ptr is None:
+        raise TypeError("%s: expected a tree handle" % fn)
+    if tree.kind not in kinds:
+        raise ValueError("%s: handle is a %s tree (needs: %s)" % (fn, tree.kind, " or ".join(kinds)))
+    return tree
+
+
+def _first_cap(rows):
+    """First guess at the pair capacity of a pair-list call; a second call is made only when K exceeds it."""
+    return max(4 * rows, 4096)
+
+
+def _pairs_call(rows, return_counts, call, exc_value=ValueError):
+    """One call with a first guess at the capacity, a second with cap = K only when K > cap -> an owned (K, 2) uint32
+    array (and the (rows,) uint32 counts).  ``call(pairs, cap, counts, K)`` returns the status."""
+    counts = np.empty(rows, dtype=np.uint32) if return_counts else None
+    cap = _first_cap(rows)
+    K = N._sz(0)
+    pairs = np.empty((cap, 2), dtype=np.uint32)
+    N.check(call(pairs, cap, counts, K), exc_value)
+    if K.value > cap:
+        cap = K.value
+        pairs = np.empty((cap, 2), dtype=np.uint32)
+        N.check(call(pairs, cap, counts, K), exc_value)
+    out = pairs[:K.value].copy()
+    return (out, counts) if return_counts else out
+
+
+def aabbtree_intersections_pairs(tree, qv, qf, return_counts=False):
+    """All pairs (i, j) of a query face i of ``qv[qf]`` and a mesh face j that intersect: (K, 2) uint32 sorted by
+    (i, j), and with ``return_counts`` the (Tq,) uint32 number of pairs of every query face (its exclusive scan
+    indexes the pairs as CSR).  The predicate is ``aabbtree_intersections_indices``'s (closed: touching counts), so
+    ``np.unique(pairs[:, 0])`` is that function's answer.  On a tree built with extra faces j also ranges over them
+    (ids after the main faces).  No reference counterpart."""
+    tree = _pairs_tree(tree, "aabbtree_intersections_pairs", ("triangles",))
+    if not isinstance(qv, np.ndarray) or not isinstance(qf, np.ndarray):
+        raise TypeError("aabbtree_intersections_pairs() arguments must be numpy.ndarray")
+    if qv.dtype != np.float64 or qv.ndim != 2:
+        raise ValueError("Query Vertices must be of type double, and 2 dimensional")
+    if qf.dtype != np.uint32 or qf.ndim != 2:
+        raise ValueError("Query Faces must be of type uint32, and 2 dimensional")
+    if qv.shape[1] != 3 or qf.shape[1] != 3:
+        raise ValueError("Input must be Nx3")
+    qv = np.ascontiguousarray(qv)
+    qf = np.ascontiguousarray(qf)
+    fn = N.lib().msh_tree_intersection_pairs
+    return _pairs_call(qf.shape[0], return_counts,
+                       lambda pairs, cap, counts, K: fn(tree.ptr, N.dptr(qv), qv.shape[0], N.uptr(qf), qf.shape[0],
+                                                        N.uptr(pairs), cap, N.uptr(counts), N.ctypes.byref(K)),
+                       Mesh_IntersectionsError)
+
+
+def _self_pairs(tree, return_counts):
+    rows = int(tree.info().n_faces)
+    fn = N.lib().msh_tree_self_intersection_pairs
+    return _pairs_call(rows, return_counts,
+                       lambda pairs, cap, counts, K: fn(tree.ptr, N.uptr(pairs), cap, N.uptr(counts),
+                                                        N.ctypes.byref(K)))
+
+
+def aabbtree_selfintersections_pairs(tree, return_counts=False):
+    """All pairs (i, j), i < j, of faces of the tree's mesh that intersect and share no exactly equal vertex
+    coordinate (the rule of ``aabb_normals.aabbtree_n_selfintersects``): (K, 2) uint32 sorted by (i, j), and with
+    ``return_counts`` the (T,) uint32 number of pairs whose smaller face is each face.  No reference counterpart."""
+    tree = _pairs_tree(tree, "aabbtree_selfintersections_pairs", ("triangles",))
+    return _self_pairs(tree, return_counts)
