@@ -186,6 +186,56 @@ int msh_tree_signed_distance_device(msh_tree* tree, const double* d_q, size_t S,
 int msh_tree_sign_from_faces_device(msh_tree* tree, const double* d_q, size_t S, const uint32_t* d_face,
                                     const uint32_t* d_part, const double* d_pt, double* d_sdist, void* stream);
 
+/* ---- generalised winding numbers: inside / outside on open meshes and soups (no reference counterpart) ----
+ * w(q) = (1 / 4 pi) sum over the tree's leaf triangles (a, b, c), taken relative to q, of the solid angle
+ *   2 atan2(a . (b x c), |a||b||c| + (a . b)|c| + (b . c)|a| + (c . a)|b|)        (Van Oosterom and Strackee 1983):
+ * 1 inside an outward-oriented closed mesh, 0 outside, fractional near openings; a row is inside iff w > 0.5.  It
+ * needs no closed, manifold or consistently oriented mesh, so it serves where the pseudonormal sign above is
+ * undefined: scans with holes, templates open at the neck or wrist, clothing layers, soups.  The sum runs over every
+ * leaf of the tree, the extra faces of msh_tree_build_ex included.  A row with a non-finite coordinate gets NaN; a
+ * row exactly on the surface gets a finite, otherwise unspecified value (the solid angle of a triangle seen from
+ * one of its own points is taken as atan2 gives it: 0 at a corner, 0 or +-2 pi in its plane).
+ *
+ * The walk (Barill et al. 2018, "Fast winding numbers for soups and clouds"): depth first from the root, child 0
+ * before child 1.  A node farther than beta r from the row -- |q - p| > beta r, p the area-weighted centroid of the
+ * node's triangles and r a radius around p that holds all their vertices -- adds its dipole (p - q) . N / (4 pi
+ * |p - q|^3), N the sum of its triangles' area vectors, and is not opened; a leaf adds its exact fp64 solid angle.
+ * Everything is accumulated in fp64 in visit order, one lane per row, so a row's answer depends on (tree, q, beta)
+ * alone: not on the other rows of the call, their order, the device split or the entry cut.
+ *   beta = 0     exact: every node is opened and every leaf evaluated (O(T) per row);
+ *   beta > 0     larger is more accurate and slower; MSH_WINDING_BETA_DEFAULT keeps |w - exact| <= 1e-2 on the test
+ *                meshes (DESIGN.md s14 has the table);
+ *   beta = +inf  no node lies farther than that: the exact walk again;
+ *   beta < 0 or NaN: MSH_EINVAL.
+ * The table behind it holds one 32-B fp32 record per internal node (p, r, N; relative to the tree's origin), built on
+ * the GPU from the stored nodes and leaves alone, bottom up: a node's fp64 sums are (child 0's) + (child 1's), a
+ * leaf's come from its own triangle -- no float atomics, the same bytes on every build.  It is built by
+ * msh_tree_winding_build or by the first query that misses it, on the handle and every replica (msh_set_devices);
+ * msh_tree_free frees it; blobs leave it out (an unpacked handle builds its own).  A tree of one face has no table
+ * (state stays 0, bytes 0) and is always evaluated exactly.
+ * Plain triangle trees only (kind 0): normals-metric, point and batched trees and NULL handles are MSH_EINVAL.
+ * S == 0 returns MSH_OK.  msh_timing_get names: "winding_build", "winding". */
+#define MSH_WINDING_BETA_DEFAULT 4.0
+typedef struct msh_winding_info {
+    int32_t state;        /* 0 none, 1 built */
+    uint32_t node_bytes;  /* bytes of one record */
+    uint32_t stack_lds;   /* per-lane stack entries held in LDS before the walk spills */
+    uint64_t bytes;       /* device bytes of the table */
+    double build_ms;      /* GPU time of its build */
+} msh_winding_info;
+int msh_tree_winding_build(msh_tree* tree);                 /* idempotent; the query calls build it when missing */
+int msh_tree_winding_info(const msh_tree* tree, msh_winding_info* info);
+/* Host arrays: q (S,3) f64 in, w (S,) f64 out; the rows go through the pinned-slab pipeline and are split over the
+ * handle's replicas as msh_tree_signed_distance's are (24 B in, 8 B out per row). */
+int msh_tree_winding_number(msh_tree* tree, const double* q, size_t S, double beta, double* w);
+/* Device pointers; asynchronous on `stream` -- except a first call that has to build the table, which is synchronous
+ * (it waits for the build and reads its status back), like the call that builds the entry cut: a caller that
+ * captures the call in a graph or needs it asynchronous calls msh_tree_winding_build first. */
+int msh_tree_winding_number_device(msh_tree* tree, const double* d_q, size_t S, double beta, double* d_w, void* stream);
+/* untimed, same walk: counts[0] nodes approximated, [1] nodes opened, [2] leaves evaluated, [3] deepest stack any row
+ * reached (entries; beyond stack_lds the walk spilled).  d_q is a device pointer; synchronous. */
+int msh_tree_winding_stats(msh_tree* tree, const double* d_q, size_t S, double beta, uint64_t counts[4]);
+
 /* The order in which the closest-point path visits the S query rows (d_perm[slot] = row): stable by the
  * Hilbert index of each row's cell in a 256^3 grid over the tree's scene box widened by 10 % per side (the cell is
  * the top 24 bits of the row's 30-bit Morton code, mapped to the Hilbert curve of the same cells; then 3 LDS radix

@@ -52,6 +52,11 @@ SIGNATURES = [
     ("msh_tree_signed_distance", _i, [_vp, _c_double_p, _sz, _c_double_p, _c_u32_p, _c_u32_p, _c_double_p]),
     ("msh_tree_signed_distance_device", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     ("msh_tree_sign_from_faces_device", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    ("msh_tree_winding_build", _i, [_vp]),
+    ("msh_tree_winding_info", _i, [_vp, _vp]),
+    ("msh_tree_winding_number", _i, [_vp, _c_double_p, _sz, ctypes.c_double, _c_double_p]),
+    ("msh_tree_winding_number_device", _i, [_vp, _vp, _sz, ctypes.c_double, _vp, _vp]),
+    ("msh_tree_winding_stats", _i, [_vp, _vp, _sz, ctypes.c_double, _c_u64_p]),
     ("msh_tree_set_entry_cut", _i, [_vp, _i]),
     ("msh_tree_query_order", _i, [_vp, _vp, _sz, _vp, _vp]),
     ("msh_tree_entry_cut_info", _i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), _c_u64_p, ctypes.POINTER(ctypes.c_double)]),
@@ -129,6 +134,16 @@ class SignInfo(ctypes.Structure):
     _fields_ = [("state", ctypes.c_int32), ("boundary_edges", ctypes.c_uint64), ("nonmanifold_edges", ctypes.c_uint64),
                 ("inconsistent_edges", ctypes.c_uint64), ("degenerate_faces", ctypes.c_uint64),
                 ("bytes", ctypes.c_uint64), ("build_ms", ctypes.c_double)]
+
+
+class WindingInfo(ctypes.Structure):
+    """msh_winding_info (include/meshsearch.h): state and layout of a tree's winding table."""
+    _fields_ = [("state", ctypes.c_int32), ("node_bytes", ctypes.c_uint32), ("stack_lds", ctypes.c_uint32),
+                ("bytes", ctypes.c_uint64), ("build_ms", ctypes.c_double)]
+
+
+# MSH_WINDING_BETA_DEFAULT (include/meshsearch.h; tests/test_winding_host.py checks that the two agree)
+WINDING_BETA_DEFAULT = 4.0
 
 
 def _preload_single_hip_runtime():
@@ -301,6 +316,27 @@ class Handle(object):
                 "nonmanifold_edges": inf.nonmanifold_edges, "inconsistent_edges": inf.inconsistent_edges,
                 "degenerate_faces": inf.degenerate_faces, "bytes": inf.bytes, "build_ms": inf.build_ms}
 
+    def winding_build(self):
+        """msh_tree_winding_build: the winding table (one dipole record per internal node), if it is not built yet;
+        the winding-number queries build it themselves when it is missing.  Returns winding_info()."""
+        check(lib().msh_tree_winding_build(self.ptr))
+        return self.winding_info()
+
+    def winding_info(self):
+        """msh_tree_winding_info -> dict(state, node_bytes, stack_lds, bytes, build_ms); state is "none" or "built"."""
+        inf = WindingInfo()
+        check(lib().msh_tree_winding_info(self.ptr, ctypes.byref(inf)))
+        return {"state": "built" if inf.state == 1 else "none", "node_bytes": inf.node_bytes,
+                "stack_lds": inf.stack_lds, "bytes": inf.bytes, "build_ms": inf.build_ms}
+
+    def winding_stats(self, d_q, S, beta=None):
+        """msh_tree_winding_stats on S device rows at address d_q -> (nodes approximated, nodes opened, leaves
+        evaluated, deepest stack any row reached); untimed, the same walk as the query."""
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().msh_tree_winding_stats(self.ptr, _vp(d_q), int(S),
+                                           WINDING_BETA_DEFAULT if beta is None else float(beta), out))
+        return tuple(int(x) for x in out)
+
     def free(self):
         if self.ptr:
             lib().msh_tree_free(self.ptr)
@@ -327,7 +363,7 @@ def source_build_id(extra=""):
     import os
     csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
     names = sorted(["sort.hip", "build.hip", "refine.hip", "nearest.hip", "rays.hip", "tritri.hip", "geometry.hip", "sign.hip",
-                    "api.cpp",
+                    "winding.hip", "api.cpp",
                     "loaders.cpp", "common.h", "internal.h"])
     h = hashlib.sha256()
     for p in [os.path.join(csrc, n) for n in names] + [os.path.join(csrc, "..", "..", "include", "meshsearch.h")]:

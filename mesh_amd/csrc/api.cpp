@@ -433,6 +433,7 @@ static void free_tree(msh_tree* t) {
     if (t->d_cut) (void)dfree(t->d_cut);
     if (t->d_face_leaf) (void)dfree(t->d_face_leaf);
     if (t->d_sign) (void)dfree(t->d_sign);
+    if (t->d_wind) (void)dfree(t->d_wind);
     for (int b = 0; b < 3; ++b) {
         if (b < 2 && t->h_stage[b]) (void)hipHostFree(t->h_stage[b]);
         if (t->d_stage[b]) (void)dfree(t->d_stage[b]);
@@ -2160,6 +2161,173 @@ int msh_tree_signed_distance(msh_tree* t, const double* q, size_t S, double* sdi
                               reinterpret_cast<double*>(d[4]), h->stream);
         });
     });
+}
+
+// ---- generalised winding numbers (winding.hip) ----
+// plain triangle trees (extra faces included: the sum runs over every leaf)
+static int check_wind_tree(const msh_tree* t, const char* fn) {
+    MSH_TRY(check_tree(t, kTriangles, fn));
+    if (t->kind != kTriangles) {
+        set_error("%s: normals-metric tree handle (winding numbers need a plain triangle tree)", fn);
+        return MSH_EINVAL;
+    }
+    return MSH_OK;
+}
+
+static int check_beta(double beta, const char* fn) {
+    if (!(beta >= 0.0)) {
+        set_error("%s: beta must be >= 0 (0: exact), got %g", fn, beta);
+        return MSH_EINVAL;
+    }
+    return MSH_OK;
+}
+
+static void free_wind_table(msh_tree* t) {
+    if (t->d_wind) {
+        (void)hipSetDevice(t->device);
+        if (t->ws_done) (void)hipEventSynchronize(t->ws_done);  // no launch may still read the table
+        (void)dfree(t->d_wind);
+    }
+    t->d_wind = nullptr;
+    t->wind = msh_winding_info{0, 0, 0, 0, 0.0};
+}
+
+// the table of one handle, if it needs one and has none (its own device and stream; scratch of its own, released on
+// return); synchronous
+static int wind_build_one(msh_tree* t) {
+    if (t->d_wind || t->T < 2 || !t->d_nodes) return MSH_OK;
+    MSH_TRY(use_device(t->device));
+    hipStream_t s = t->stream;
+    const size_t bytes = winding_table_bytes(t->T);
+    void* block = nullptr;
+    MSH_HIP(dmalloc(&block, bytes));
+    Workspace ws;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    uint32_t h[2] = {0, 0};
+    float ms = 0.f;
+    int st = MSH_OK;
+    do {
+        hipError_t e = hipEventCreate(&e0);
+        if (e == hipSuccess) e = hipEventCreate(&e1);
+        if (e != hipSuccess) { set_error("msh_tree_winding_build: %s", hipGetErrorString(e)); st = MSH_EDEVICE; break; }
+        if ((st = ws.counters.reserve(sizeof(h))) != MSH_OK) break;
+        e = hipMemsetAsync(ws.counters.ptr, 0, sizeof(h), s);
+        if (e == hipSuccess) e = hipEventRecord(e0, s);
+        if (e != hipSuccess) { set_error("msh_tree_winding_build: %s", hipGetErrorString(e)); st = MSH_EDEVICE; break; }
+        if ((st = winding_table_build(t, block, ws.counters.as<uint32_t>(), ws, s)) != MSH_OK) break;
+        e = hipEventRecord(e1, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(h, ws.counters.ptr, sizeof(h), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { set_error("msh_tree_winding_build: %s", hipGetErrorString(e)); st = MSH_EDEVICE; break; }
+        (void)hipEventElapsedTime(&ms, e0, e1);
+    } while (0);
+    (void)hipStreamSynchronize(s);  // the scratch below is released on return
+    ws.release();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (st == MSH_OK && (h[0] & 1u)) {
+        set_error("msh_tree_winding_build: a node's child reference lies outside the tree (corrupt tree)");
+        st = MSH_EDEVICE;
+    }
+    if (st == MSH_OK && h[1] == 0u) {
+        set_error("msh_tree_winding_build: the tree is deeper than its recorded depth %d (corrupt tree)", t->max_depth);
+        st = MSH_EDEVICE;
+    }
+    if (st != MSH_OK) {
+        (void)dfree(block);
+        return st;
+    }
+    t->d_wind = block;
+    t->wind = msh_winding_info{1, (uint32_t)kWindRecBytes, (uint32_t)winding_stack_lds(), bytes, ms};
+    return MSH_OK;
+}
+
+// the handle and its replicas: all or none (the host entry point splits its rows over every replica)
+static int wind_build_all(msh_tree* t) {
+    int st = wind_build_one(t);
+    for (size_t g = 0; g < t->replicas.size() && st == MSH_OK; ++g) st = wind_build_one(t->replicas[g]);
+    if (st != MSH_OK) {
+        const std::string keep = g_err;
+        free_wind_table(t);
+        for (msh_tree* r : t->replicas) free_wind_table(r);
+        g_err = keep;
+    }
+    (void)use_device(t->device);
+    return st;
+}
+
+int msh_tree_winding_build(msh_tree* t) {
+    MSH_TRY(check_wind_tree(t, "msh_tree_winding_build"));
+    return wind_build_all(t);
+}
+
+int msh_tree_winding_info(const msh_tree* t, msh_winding_info* info) {
+    if (!t || !info) { set_error("msh_tree_winding_info: null argument"); return MSH_EINVAL; }
+    *info = t->wind;
+    info->node_bytes = (uint32_t)kWindRecBytes;
+    info->stack_lds = (uint32_t)winding_stack_lds();
+    return MSH_OK;
+}
+
+// one launch over d_q in the closest-point path's slot order (the table is built)
+static int winding_run(msh_tree* t, const double* d_q, size_t S, double beta, double* d_w, hipStream_t s) {
+    WsOrder order(t, s);
+    QueryOrder ord;
+    MSH_TRY(sort_queries(t, d_q, nullptr, S, s, &ord, true));
+    return launch_winding(t, t->d_wind, ord, S, beta, d_w, s);
+}
+
+int msh_tree_winding_number_device(msh_tree* t, const double* d_q, size_t S, double beta, double* d_w, void* stream) {
+    MSH_TRY(check_beta(beta, "msh_tree_winding_number_device"));  // before the handle: a bad beta is refused on any of them
+    MSH_TRY(check_wind_tree(t, "msh_tree_winding_number_device"));
+    MSH_TRY(check_count(S, "msh_tree_winding_number_device"));
+    if (S == 0) return MSH_OK;
+    if (!d_q || !d_w) { set_error("msh_tree_winding_number_device: null argument"); return MSH_EINVAL; }
+    MSH_TRY(wind_build_one(t));
+    return winding_run(t, d_q, S, beta, d_w, pick(t, stream));
+}
+
+int msh_tree_winding_number(msh_tree* t, const double* q, size_t S, double beta, double* w) {
+    MSH_TRY(check_beta(beta, "msh_tree_winding_number"));  // before the handle: a bad beta is refused on any of them
+    MSH_TRY(check_wind_tree(t, "msh_tree_winding_number"));
+    MSH_TRY(check_count(S, "msh_tree_winding_number"));
+    if (S == 0) return MSH_OK;
+    if (!q || !w) { set_error("msh_tree_winding_number: null argument"); return MSH_EINVAL; }
+    MSH_TRY(wind_build_all(t));
+    return fan_out(t, S, 32, [&](msh_tree* h, size_t r0, size_t S_h) {
+        MSH_TRY(use_device(h->device));
+        // rows: q (24 B in) | w (8 B out)
+        const std::vector<HostArr> arrs = {{q + 3 * r0, nullptr, 24}, {nullptr, w + r0, 8}};
+        return pipelined(h, S_h, arrs, [&](size_t, size_t n, const std::vector<char*>& d) {
+            return winding_run(h, reinterpret_cast<const double*>(d[0]), n, beta, reinterpret_cast<double*>(d[1]),
+                               h->stream);
+        });
+    });
+}
+
+int msh_tree_winding_stats(msh_tree* t, const double* d_q, size_t S, double beta, uint64_t counts[4]) {
+    MSH_TRY(check_beta(beta, "msh_tree_winding_stats"));  // before the handle: a bad beta is refused on any of them
+    MSH_TRY(check_wind_tree(t, "msh_tree_winding_stats"));
+    MSH_TRY(check_count(S, "msh_tree_winding_stats"));
+    if (!counts) { set_error("msh_tree_winding_stats: null argument"); return MSH_EINVAL; }
+    for (int k = 0; k < 4; ++k) counts[k] = 0;
+    if (S == 0) return MSH_OK;
+    if (!d_q) { set_error("msh_tree_winding_stats: null argument"); return MSH_EINVAL; }
+    MSH_TRY(wind_build_one(t));
+    hipStream_t s = t->stream;
+    unsigned long long h[4] = {0, 0, 0, 0};
+    {
+        WsOrder order(t, s);
+        QueryOrder ord;
+        MSH_TRY(sort_queries(t, d_q, nullptr, S, s, &ord, true));
+        MSH_TRY(t->ws.stats.reserve(sizeof(h)));
+        MSH_HIP(hipMemsetAsync(t->ws.stats.ptr, 0, sizeof(h), s));
+        MSH_TRY(launch_winding_stats(t, t->d_wind, ord, S, beta, t->ws.stats.as<unsigned long long>(), s));
+        MSH_HIP(hipMemcpyAsync(h, t->ws.stats.ptr, sizeof(h), hipMemcpyDeviceToHost, s));
+    }
+    MSH_HIP(hipStreamSynchronize(s));
+    for (int k = 0; k < 4; ++k) counts[k] = h[k];
+    return MSH_OK;
 }
 
 // the rays' walks start from the tree's entry cut (built by the automatic policy on these rows too: rays_cut)

@@ -542,18 +542,21 @@ __device__ inline uint2 stack_get(const uint2* __restrict__ lds, const uint2* __
 }
 // 4-B entries (compact stacks, trees of <= 2^20 leaves): the same placement; the spill side takes a 64-bit slot
 // like the 8-B stack's (a 32-bit access let the compiler merge both sides into one flat access)
+// (D: the LDS depth; the winding-number walk keeps a shallower one, winding.hip kWindStack)
+template <int D = kStack>
 __device__ inline void stack_put(uint32_t* __restrict__ lds, uint2* __restrict__ spill, int sp, uint32_t e) {
-    if (sp < kStack) {
+    if (sp < D) {
         lds[sp * kBlock] = e;
     } else {
         __builtin_nontemporal_store((unsigned long long)e,
-                                    reinterpret_cast<unsigned long long*>(spill + (size_t)(sp - kStack) * kBlock));
+                                    reinterpret_cast<unsigned long long*>(spill + (size_t)(sp - D) * kBlock));
     }
 }
+template <int D = kStack>
 __device__ inline uint32_t stack_get(const uint32_t* __restrict__ lds, const uint2* __restrict__ spill, int sp) {
-    if (sp < kStack) return lds[sp * kBlock];
+    if (sp < D) return lds[sp * kBlock];
     return (uint32_t)__builtin_nontemporal_load(
-        reinterpret_cast<const unsigned long long*>(spill + (size_t)(sp - kStack) * kBlock));
+        reinterpret_cast<const unsigned long long*>(spill + (size_t)(sp - D) * kBlock));
 }
 
 // 30-bit Morton code of a query point in the box [l, h] (fp32 cell coordinates, 1024 cells per axis, clamped)

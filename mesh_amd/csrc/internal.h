@@ -161,6 +161,10 @@ struct msh_tree {
     // and f (T,3) u32 in that order; nullptr until built (blobs leave it out)
     void* d_sign = nullptr;
     msh_sign_info sign = {0, 0, 0, 0, 0, 0, 0.0};
+    // winding table (msh_tree_winding_build; winding.hip): T - 1 dipole records of kWindRecBytes; nullptr until built
+    // (lazily, by the first winding-number query; trees of one leaf never hold one; blobs leave it out)
+    void* d_wind = nullptr;
+    msh_winding_info wind = {0, 0, 0, 0, 0.0};
     int cut_G = 0;
     // lazily built on the first closest-point query (msh_tree_set_entry_cut): requested grid (< 0 automatic,
     // 0 off), state (0 pending, 1 built, 2 off / not applicable, 3 failed), GPU build time
@@ -356,6 +360,27 @@ int sign_table_build(const msh_tree* tree, const uint32_t* d_f, void* block, uin
 // NaN for face >= T
 int launch_sign_pass(const SignTable& tab, size_t T, size_t P, const double* d_q, size_t S, const uint32_t* d_face,
                      const uint32_t* d_part, const double* d_pt, double* d_sdist, hipStream_t s);
+
+// ---- generalised winding numbers (winding.hip) ----
+// The winding table of a triangle tree: one 32-B record per internal node, the dipole of its subtree (area-weighted
+// centroid, a radius around it that holds the subtree's vertices, the sum of the area vectors; fp32, relative to the
+// tree's origin).
+constexpr size_t kWindRecBytes = 32;
+inline size_t winding_table_bytes(size_t T) { return T > 1 ? (T - 1) * kWindRecBytes : 0; }
+// per-lane stack entries the walk keeps in LDS before it spills
+int winding_stack_lds();
+// Fills `block` (winding_table_bytes(T), 16-B aligned) from d_nodes and the leaves alone: max_depth sweeps, each
+// computing the nodes whose children are done.  d_err (2 u32, zeroed by the caller): [0] bit 0 = a child reference
+// outside the tree, [1] = the root's sweep (0: never reached, the tree is deeper than max_depth).  Asynchronous on s.
+int winding_table_build(const msh_tree* tree, void* block, uint32_t* d_err, Workspace& ws, hipStream_t s);
+// w[row] = the winding number of q[row] (NaN for a non-finite row); ord: the rows' slot order (lazy: ord.q are the
+// caller's rows).  beta = 0: every node is opened.  table: the tree's records (unused when T == 1).  Uses ws.spill.
+int launch_winding(msh_tree* tree, const void* table, const QueryOrder& ord, size_t S, double beta, double* d_w,
+                   hipStream_t s);
+// the same walk, untimed, no answers: d_counts[0] += nodes approximated, [1] += nodes opened, [2] += leaves evaluated,
+// [3] = max(the deepest stack any row reached)
+int launch_winding_stats(msh_tree* tree, const void* table, const QueryOrder& ord, size_t S, double beta,
+                         unsigned long long* d_counts, hipStream_t s);
 
 // ---- timing ----
 struct TimedLaunch {

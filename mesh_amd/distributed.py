@@ -295,6 +295,15 @@ def signed_distance_device(tree, q, sdist, face, part, pt, stream=None):
         part.data_ptr() if part is not None else None, pt.data_ptr(), _stream(q, stream)))
 
 
+def winding_number_device(tree, q, w, beta=None, stream=None):
+    """Device-resident generalised winding numbers (msh_tree_winding_number_device) on torch tensors: q (S,3) f64,
+    w (S,) f64; beta None: the library default, 0: exact.  Asynchronous on `stream` (default: torch's current stream),
+    except a first call that has to build the tree's winding table (tree.winding_build() beforehand avoids that)."""
+    _native.check(_native.lib().msh_tree_winding_number_device(
+        tree.ptr, q.data_ptr(), q.shape[0], _native.WINDING_BETA_DEFAULT if beta is None else float(beta),
+        w.data_ptr(), _stream(q, stream)))
+
+
 def sign_from_faces_device(tree, q, face, part, pt, sdist, stream=None):
     """The sign pass alone (msh_tree_sign_from_faces_device): sdist (S,) f64 for given (face, part, point) rows, e.g.
     the rows NarrowRing rebuilt with points_from_faces_device.  Asynchronous on `stream`."""

@@ -183,9 +183,20 @@ class Mesh(object):
         Raises ValueError unless the mesh is a closed, consistently oriented manifold."""
         return self._tree_for_batch(vertices).signed_distance(vertices)[0]
 
-    def contains(self, vertices):
-        """bool (S,): whether each row of `vertices` lies inside this (closed, outward-oriented) mesh."""
-        return self._tree_for_batch(vertices).contains(vertices)
+    def contains(self, vertices, method="pseudonormal"):
+        """bool (S,): whether each row of `vertices` lies inside this (closed, outward-oriented) mesh.
+        method="winding": by the generalised winding number (> 0.5), also on open meshes and soups."""
+        if method == "winding":
+            return self.compute_aabb_tree().contains(vertices, method=method)
+        if method != "pseudonormal":
+            raise ValueError("contains: method must be 'pseudonormal' or 'winding', got %r" % (method,))
+        return self._tree_for_batch(vertices).contains(vertices, method=method)
+
+    def winding_numbers(self, vertices, beta=None):
+        """Generalised winding number of every row of `vertices` about this mesh, (S,) float64: 1 inside an
+        outward-oriented closed mesh, 0 outside, fractional near openings (search.AabbTree.winding_number on a tree
+        built for this call; the walk does not use the entry cut, so none is asked for)."""
+        return self.compute_aabb_tree().winding_number(vertices, beta)
 
     def self_intersection_pairs(self):
         """(K, 2) uint32, sorted: the pairs (i, j), i < j, of faces of this mesh that intersect and share no exactly

@@ -71,15 +71,41 @@ class AabbTree(object):
         return dict((k, info[k]) for k in ("boundary_edges", "nonmanifold_edges", "inconsistent_edges",
                                            "degenerate_faces"))
 
-    def signed_distance(self, v_samples, check=True):
+    def winding_number(self, v_samples, beta=None):
+        """w (S,) f64: the generalised winding number of each sample -- 1 inside an outward-oriented closed mesh,
+        0 outside, fractional near openings; inside iff ``w > 0.5``.  Defined on open meshes and soups too.
+        ``beta``: accuracy of the far-field approximation (0 exact, larger more accurate; ``None`` the library
+        default, error <= 1e-2)."""
+        from . import spatialsearch
+        return spatialsearch.aabbtree_winding_number(self.cpp_handle, _f64c(v_samples), beta)
+
+    def signed_distance(self, v_samples, check=True, sign="pseudonormal"):
         """(sdist (S,) f64, face (S,) u32, point (S,3) f64): the closest face and point of ``nearest`` and the
         signed distance to it, negative inside an outward-oriented mesh (angle-weighted pseudonormal test).
 
         With ``check=True`` a mesh that is not a closed, consistently oriented manifold raises ValueError naming
         the counts of ``orientation_info``.  With ``check=False`` the query runs anyway: a boundary or non-manifold
         edge uses its own face's normal, an inconsistent edge the sum of both, a degenerate face a zero normal,
-        and the sign is undefined near those features."""
+        and the sign is undefined near those features.
+
+        ``sign="winding"`` takes the sign from the generalised winding number instead (negative where
+        ``winding_number > 0.5``): no orientation check is made and ``check`` is ignored, so open meshes and soups
+        are answered.  Magnitude, face and point are ``nearest``'s; rows at distance 0 stay +0.0, non-finite rows
+        NaN."""
         from . import spatialsearch
+        if sign == "winding":
+            q = _f64c(v_samples)
+            face, pt = self.nearest(q)
+            face = face.reshape(-1)
+            d = q.reshape(-1, 3) - pt
+            # the sign pass's magnitude, operation for operation (msh_tree_signed_distance)
+            sdist = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+            sdist[face == N.NO_FACE] = np.nan
+            inside = (self.winding_number(q) > 0.5) & (sdist > 0)
+            sdist[inside] = -sdist[inside]
+            return sdist, face, pt
+        if sign != "pseudonormal":
+            raise ValueError("signed_distance: sign must be 'pseudonormal' or 'winding', got %r" % (sign,))
         if check:
             bad = dict((k, n) for k, n in self.orientation_info().items() if n)
             if bad:
@@ -88,9 +114,14 @@ class AabbTree(object):
         sdist, face, _, pt = spatialsearch.aabbtree_signed_distance(self.cpp_handle, _f64c(v_samples))
         return sdist, face, pt
 
-    def contains(self, v_samples, check=True):
+    def contains(self, v_samples, check=True, method="pseudonormal"):
         """bool (S,): whether each sample lies inside the mesh (``signed_distance < 0``; points on the surface
-        and non-finite rows are not inside)."""
+        and non-finite rows are not inside).  ``method="winding"``: ``winding_number > 0.5`` instead -- no
+        orientation check (``check`` is ignored), defined on open meshes and soups."""
+        if method == "winding":
+            return self.winding_number(v_samples) > 0.5
+        if method != "pseudonormal":
+            raise ValueError("contains: method must be 'pseudonormal' or 'winding', got %r" % (method,))
         return self.signed_distance(v_samples, check)[0] < 0
 
     def intersections_indices(self, q_v, q_f):

@@ -10,7 +10,8 @@ constructions).  Deliberate differences:
   * ``aabbtree_intersections_indices`` is registered and returns ascending indices (reference: not in
     the method table, :35-40, and racy push_back, :393-402).
 Beyond the reference: ``aabbtree_intersections_pairs`` / ``aabbtree_selfintersections_pairs`` return which face
-hits which face, as a sorted (K, 2) pair list.
+hits which face, as a sorted (K, 2) pair list; ``aabbtree_signed_distance`` and ``aabbtree_winding_number`` answer
+inside / outside, the first on closed manifold meshes, the second on any triangle set.
 """
 import numpy as np
 
@@ -91,6 +92,31 @@ def aabbtree_signed_distance(tree, q):
     N.check(N.lib().msh_tree_signed_distance(tree.ptr, N.dptr(q), S, N.dptr(sdist), N.uptr(face), N.uptr(part),
                                              N.dptr(pt)))
     return sdist, face, part, pt
+
+
+def aabbtree_winding_number(tree, q, beta=None):
+    """w (S,) float64: the generalised winding number of every row of ``q`` about the tree's triangles -- 1 inside an
+    outward-oriented closed mesh, 0 outside, fractional near openings; a row is inside iff ``w > 0.5``; NaN on
+    non-finite rows (no reference counterpart).
+
+    It needs no closed or manifold mesh (scans with holes, open templates, soups).  ``beta`` is the accuracy of the
+    far-field approximation (Barill et al. 2018): a subtree farther than ``beta`` times its radius contributes its
+    dipole; larger is more accurate and slower, 0 is exact (every triangle evaluated), ``None`` the library default
+    (error <= 1e-2).  A row exactly on the surface gets a finite, otherwise unspecified value.  The table behind it
+    is built on first use from the tree itself."""
+    tree = _tree(tree, "aabbtree_winding_number")
+    if not isinstance(q, np.ndarray):
+        raise TypeError("aabbtree_winding_number() argument 2 must be numpy.ndarray")
+    if q.ndim != 2 or q.shape[1] != 3:
+        raise ValueError("Input must be Nx3")
+    if tree.kind != "triangles":
+        raise TypeError("aabbtree_winding_number: handle is not a triangle tree")
+    beta = N.WINDING_BETA_DEFAULT if beta is None else float(beta)
+    q = np.ascontiguousarray(q, dtype=np.float64)
+    S = q.shape[0]
+    w, = N.empty_results(((S,), np.float64))
+    N.check(N.lib().msh_tree_winding_number(tree.ptr, N.dptr(q), S, beta, N.dptr(w)))
+    return w
 
 
 def aabbtree_nearest_barycentric(tree, q):
