@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <chrono>
 #include <string>
 #include <vector>
 
@@ -30,7 +31,7 @@ void set_error(const char* fmt, ...);
         if (_s != MSH_OK) return _s; \
     } while (0)
 
-// Device allocations through the library's cache (api.cpp DevCache): dfree keeps the block for the next request of a
+// Device allocations through the library's cache (devmem.cpp DevCache): dfree keeps the block for the next request of a
 // similar size on its device (after waiting for the device, as hipFree does).
 hipError_t dmalloc_raw(void** p, size_t bytes);
 hipError_t dfree(void* p);
@@ -117,6 +118,16 @@ struct QueryOrder {
     bool gathered = true;
 };
 
+// Staging slabs of one pipelined host call (hostpipe.cpp): two pinned host slabs of hbytes, a ring of three device
+// slabs of dbytes.  A plain value: the handle holds the set it leased, the pool (StagePool) the idle ones.
+struct StageSet {
+    void* h[2] = {nullptr, nullptr};
+    void* d[3] = {nullptr, nullptr, nullptr};
+    size_t hbytes = 0, dbytes = 0;  // host slabs hold the inputs only when results go straight into pinned arrays
+    void free_host();    // hostpipe.cpp
+    void free_device();  // (the caller is on the slabs' device)
+};
+
 }  // namespace msh
 
 struct msh_tree {
@@ -140,18 +151,15 @@ struct msh_tree {
     size_t vshard_v0 = 0, vshard_nv = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ws_done = nullptr;  // recorded after the last launch that used `ws` (stream ordering)
-    // host-call staging (lazily created, grow-only): two pinned host slabs, two device slabs, copy
-    // streams and their events (api.cpp pipelined())
-    void* h_stage[2] = {nullptr, nullptr};
-    void* d_stage[3] = {nullptr, nullptr, nullptr};  // device slabs: a ring of 3 (pipelined)
-    size_t stage_bytes = 0;   // device slabs
-    size_t hstage_bytes = 0;  // host slabs (inputs only when results go straight into pinned arrays)
+    // host-call staging (hostpipe.cpp pipelined()): the slab set leased from the pool for one call, and the copy
+    // streams and their events (lazily created)
+    msh::StageSet stage;
     hipStream_t s_up = nullptr, s_down = nullptr;
     hipEvent_t e_up[3] = {nullptr, nullptr, nullptr}, e_run[3] = {nullptr, nullptr, nullptr},
                e_down[3] = {nullptr, nullptr, nullptr};
     double build_ms = 0.0;
     int max_depth = 0;             // bound of the deepest leaf (root children = 1): k_karras prefix lengths
-    // entry cut (single triangle trees; api.cpp build_entry_cut): a G^3 grid over the scene box widened by 1/4, one
+    // entry cut (single triangle trees; entrycut.cpp build_entry_cut): a G^3 grid over the scene box widened by 1/4, one
     // record per cell -- its hint leaf and kCutK start entries, 32 B (4-B entries, trees of <= 2^20 leaves) or 64 B
     // (cut_wide) --; d_cut == nullptr: every query starts at the root
     uint32_t* d_cut = nullptr;
@@ -264,7 +272,7 @@ int cut_centres(int G, const double* lo, const double* w, double* d_q, hipStream
 // MESH_AMD_CUT_SUBDIV = 0 / 1 / 2 overrides it); < 0: the ball rule alone.  d_nflag (nullable): incremented by the
 // number of records the drop shortened
 constexpr int kCutSubdiv = 2;         // the deepest split of a cell into octants
-constexpr int kCutSubdivDefault = 2;  // the depth of a grid the caller asked for (api.cpp ensure_entry_cut)
+constexpr int kCutSubdivDefault = 2;  // the depth of a grid the caller asked for (entrycut.cpp ensure_entry_cut)
 int cut_level(const msh_tree* tree, int G, const double* lo, const double* w, const double* d_pts, const int* d_hint,
               uint32_t* d_rec, bool e4, hipStream_t s, const uint32_t* d_half = nullptr,
               unsigned long long* d_nflag = nullptr, int subdiv = 0);
@@ -382,7 +390,7 @@ int launch_winding(msh_tree* tree, const void* table, const QueryOrder& ord, siz
 int launch_winding_stats(msh_tree* tree, const void* table, const QueryOrder& ord, size_t S, double beta,
                          unsigned long long* d_counts, hipStream_t s);
 
-// ---- timing ----
+// ---- timing (devmem.cpp) ----
 struct TimedLaunch {
     const char* name;
     hipStream_t s;
@@ -390,5 +398,63 @@ struct TimedLaunch {
     TimedLaunch(const char* n, hipStream_t st);
     ~TimedLaunch();
 };
+// host-side intervals under the same names (msh_timing_get): the host pipeline's copies and waits
+void host_time(const char* name, std::chrono::steady_clock::time_point t0);
+
+// ---- the host layer: devmem.cpp (device state, the handle), entrycut.cpp, blob.cpp; hostpipe.h has the pipeline ----
+extern thread_local std::string g_err;          // msh_last_error
+extern thread_local int g_device;               // msh_set_device (-1: the runtime's current device)
+extern thread_local std::vector<int> g_devices;  // devices of the trees built next on this thread (msh_set_devices)
+int use_device(int dev);
+int current_device(int* dev);
+// query workspaces handed from a freed triangle tree to the next one built on the device (devmem.cpp WsPool)
+void ws_pool_take(int dev, Workspace& ws);
+size_t ws_pool_trim();
+size_t ws_pool_bytes();
+int new_tree(int kind, msh_tree** out);
+void free_tree(msh_tree* t);
+int return_tree(msh_tree* t, int st, msh_tree** out);  // end of a build: *out = t, or t freed and the build's error kept
+int finish_pending(msh_tree* t);  // end of an asynchronous batched build
+
+template <class T>
+inline int upload(DevBuf& buf, const T* host, size_t n, hipStream_t s) {
+    MSH_TRY(buf.reserve(n * sizeof(T)));
+    if (n) MSH_HIP(hipMemcpyAsync(buf.ptr, host, n * sizeof(T), hipMemcpyHostToDevice, s));
+    return MSH_OK;
+}
+
+// Stream ordering of the handle's workspace: every launch sequence that uses `ws` first waits for the
+// previous one (whatever stream it ran on) and then marks its own end, so a *_device call on a
+// caller's stream followed by any other call on the same handle cannot overwrite scratch still in use.
+struct WsOrder {
+    msh_tree* t;
+    hipStream_t s;
+    WsOrder(msh_tree* tree, hipStream_t st) : t(tree), s(st) {
+        if (t->ws_done) (void)hipStreamWaitEvent(s, t->ws_done, 0);
+    }
+    ~WsOrder() {
+        if (t->ws_done) (void)hipEventRecord(t->ws_done, s);
+    }
+};
+
+// frees a buffer the handle's launches read (entry cut, sign and winding tables) once none may still read it
+template <class T>
+inline void free_after_use(msh_tree* t, T*& p) {
+    if (p) {
+        (void)hipSetDevice(t->device);
+        if (t->ws_done) (void)hipEventSynchronize(t->ws_done);
+        (void)dfree(p);
+    }
+    p = nullptr;
+}
+
+// entry cut (entrycut.cpp): states of msh_tree::cut_state, and the policy's entry points
+enum { kCutPending = 0, kCutBuilt = 1, kCutOff = 2, kCutFailed = 3 };
+bool cut_applies(const msh_tree* t);
+void free_entry_cut(msh_tree* t);
+void ensure_entry_cut(msh_tree* t, size_t S);  // before a closest-point or alongnormal call of S rows
+
+// copies of a freshly built tree on the other devices of the calling thread's device list (blob.cpp)
+int replicate_tree(msh_tree* t);
 
 }  // namespace msh

@@ -140,6 +140,25 @@ def test_child_box_bound_is_conservative(tmp_path, mutation):
         assert out.returncode == 1 and viol > 0, line
 
 
+@pytest.mark.parametrize("sanitize", [False, True])
+def test_host_plan_and_layout(tmp_path, sanitize):
+    """The planning of a host-buffer call (mesh_amd/csrc/hostplan.h, no HIP call in it) as a plain host program: the
+    chunks of a plan tile [0, S) in order with none empty and the slab is the largest; every entry point's column
+    set has prefix-sum slab offsets with the inputs first and the row width the fan-out threshold was given before
+    (56, 76, 64, 32, 84, 76, 36, 12 P); shards are contiguous, covering and balanced.  Once more with AddressSanitizer
+    and UBSan in the program itself."""
+    import subprocess
+    exe = str(tmp_path / "hostplan_check")
+    cmd = ["/opt/rocm/bin/hipcc", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-x", "c++",
+           os.path.join(ROOT, "tests", "csrc", "hostplan_check.cpp"), "-I", os.path.join(ROOT, "mesh_amd", "csrc"),
+           "-o", exe]
+    if sanitize:
+        cmd[1:1] = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
+    subprocess.check_call(cmd)
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "hostplan_check: 0 failures" in out.stdout, out.stdout + out.stderr
+
+
 def test_batch_build_validation():
     # argument checks run on the host, before any device work
     from mesh_amd import _native

@@ -72,12 +72,12 @@ def _assert_equal(got, want, what):
 
 
 def _auto_G(f):
-    # api.cpp cut_grid: the fine automatic grid, twice the coarse one's resolution (8 cells per face, at least 16^3)
+    # entrycut.cpp cut_grid: the fine automatic grid, twice the coarse one's resolution (8 cells per face, at least 16^3)
     return 2 * max(16, int(round(np.cbrt(8 * f.shape[0]))))
 
 
 def _grid_planes(v, G):
-    # api.cpp build_entry_cut: the scene box (fp32 bounds of the vertices) widened by 1/4, G cells per axis
+    # entrycut.cpp build_entry_cut: the scene box (fp32 bounds of the vertices) widened by 1/4, G cells per axis
     lo32, hi32 = v.astype(np.float32).min(0).astype(np.float64), v.astype(np.float32).max(0).astype(np.float64)
     half = 0.5 * (hi32 - lo32)
     m = 0.5 * (hi32 + lo32)

@@ -5,7 +5,7 @@ the closest-point path (lean and generic kernels, 32-B and 64-B records, grids w
 comparable to the queries' distance d to far below it, the two-stage fine grid) and on the alongnormal path, whose
 rays start at the root in a cell the rule shortened (the record's flag).
 
-Trees under 4096 faces take no entry cut at all (api.cpp kCutMinLeaves), so the small meshes of the list below (the
+Trees under 4096 faces take no entry cut at all (entrycut.cpp kCutMinLeaves), so the small meshes of the list below (the
 640-face icosphere, the 16 x 16 flat grid, the two-triangle mesh, the small mesh with a zero-area face) only pin that
 nothing changes for them; a 48 x 48 flat grid and the 5120-face icosphere with a zero-area face added put the same
 geometry (foot points on boundary edges, a degenerate face) through a built cut.
@@ -66,7 +66,7 @@ def _mesh(name):
 
 
 def _grid_box(v):
-    # api.cpp build_entry_cut: the scene box widened by 1/4 (an axis at least 5 % of the largest)
+    # entrycut.cpp build_entry_cut: the scene box widened by 1/4 (an axis at least 5 % of the largest)
     lo, hi = v.min(0), v.max(0)
     half = 0.5 * (hi - lo)
     e = 1.25 * np.maximum(half, 0.05 * half.max())
@@ -131,7 +131,7 @@ def test_directional_cut_bit_exact(oracle, monkeypatch, name):
     cut = f.shape[0] >= 4096
     flagged = 0
     for g in (16, 32, 64, -1):
-        # the grid the fine automatic request builds (api.cpp cut_grid): twice the coarse one's cells per axis
+        # the grid the fine automatic request builds (entrycut.cpp cut_grid): twice the coarse one's cells per axis
         G = g if g > 0 else 2 * max(16, int(round(np.cbrt(min(8 * f.shape[0], 1 << 23)))))
         q = _queries(v, f, G, seed=100 + abs(g))
         t.set_entry_cut(0)

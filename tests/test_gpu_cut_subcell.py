@@ -49,7 +49,7 @@ def _mesh(name):
 
 
 def _grid(g, T):
-    # the grid the fine automatic request builds (api.cpp cut_grid): twice the coarse one's cells per axis
+    # the grid the fine automatic request builds (entrycut.cpp cut_grid): twice the coarse one's cells per axis
     return g if g > 0 else 2 * max(16, int(round(np.cbrt(min(8 * T, 1 << 23)))))
 
 
@@ -178,7 +178,7 @@ def test_subcell_depth_of_automatic_and_requested_grids(monkeypatch):
     f = np.ascontiguousarray(f, np.uint32)
     G = _grid(-1, f.shape[0])
     glo, ext = D._grid_box(v)
-    # api.cpp: the fine grid once the handle has answered 16 rows per fine cell (64 cells per leaf)
+    # entrycut.cpp: the fine grid once the handle has answered 16 rows per fine cell (64 cells per leaf)
     rows = 16 * 64 * f.shape[0] + 4096
     q = np.ascontiguousarray(glo + np.random.default_rng(21).uniform(0, 1, (rows, 3)) * ext)
     t = spatialsearch.aabbtree_compute(v, f)

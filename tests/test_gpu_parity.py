@@ -197,7 +197,7 @@ def test_pass2_heavy_items_split(oracle):
 
 
 def test_workspace_handoff_between_trees(oracle, meshes):
-    # a freed triangle tree hands its query workspace to the next tree built on the device (api.cpp WsPool), as
+    # a freed triangle tree hands its query workspace to the next tree built on the device (devmem.cpp WsPool), as
     # a tree per call (Mesh.closest_faces_and_points) does: trees built and freed in turn on two meshes answer
     # the same arrays every round, and match brute force
     import gc
@@ -236,7 +236,7 @@ def test_entry_cut_bit_exact(oracle, monkeypatch):
     from mesh_amd import spatialsearch
     v, f = W.c3_mesh()
     rng = np.random.default_rng(41)
-    G = int(round(np.cbrt(min(64 * f.shape[0], 1 << 26))))  # api.cpp cut_grid: the fine automatic grid
+    G = int(round(np.cbrt(min(64 * f.shape[0], 1 << 26))))  # entrycut.cpp cut_grid: the fine automatic grid
     assert G == 400
     lo, w = -1.25, 2.5 / G  # scene box +-1 (icosphere vertices on the unit sphere), widened by 1/4
     on_faces = rng.uniform(-1.2, 1.2, (20_000, 3))
@@ -343,7 +343,7 @@ def test_entry_cut_lazy_and_failure_fallback(oracle):
 def test_entry_cut_rebuild_memory_flat():
     # Rebuilding the entry cut (set_entry_cut(-1) then a query) frees its build temporaries (~420 MB of cell-centre
     # queries and answers on C3): device memory is flat across cycles.  msh_device_pool_trim then frees the idle
-    # query workspace a freed tree leaves to the next one (api.cpp WsPool).
+    # query workspace a freed tree leaves to the next one (devmem.cpp WsPool).
     import gc
     import torch
     from mesh_amd import _native as N, spatialsearch

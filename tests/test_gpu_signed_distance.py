@@ -371,6 +371,58 @@ def test_device_path_equals_host(case):
     assert np.array_equal(pt_np.cpu().numpy(), host[3], equal_nan=True)
 
 
+def test_chunked_host_call_equals_device(meshes, monkeypatch):
+    """A host call above the 16 MB small-call limit runs the chunk pipeline: 300,000 rows on the golden sphere are
+    19.2 MB at 64 B per row, and MESH_AMD_HOST_CHUNK = 131072 makes three chunks, the last ragged.  Its four arrays
+    equal msh_tree_signed_distance_device on the same rows, with results carved from the pinned pool (downloaded in
+    place), with the pool off (staged), with the caller's arrays registered in place, and with part == NULL (the
+    part slab is then the sign pass's scratch and is not downloaded)."""
+    import torch
+    from mesh_amd import _native as N, distributed, spatialsearch
+    v, f = closed_mesh(meshes, "sphere")
+    S = 300000
+    lo, hi = v.min(0), v.max(0)
+    q = np.random.default_rng(31).uniform(lo - 0.2 * (hi - lo), hi + 0.2 * (hi - lo), (S, 3))
+    assert 64 * S > 16 << 20
+    monkeypatch.setenv("MESH_AMD_HOST_CHUNK", "131072")
+    monkeypatch.setattr(N, "PINNED_MIN_BYTES", 1 << 20)
+    t = tree_of(v, f)
+    t.sign_build()
+    d_q = torch.from_numpy(q).to("cuda:0")
+    mk = lambda *shape, dt: torch.empty(shape, dtype=dt, device="cuda:0")
+    sd, face, part, pt = mk(S, dt=torch.float64), mk(S, dt=torch.int32), mk(S, dt=torch.int32), mk(S, 3, dt=torch.float64)
+    distributed.signed_distance_device(t, d_q, sd, face, part, pt)
+    torch.cuda.synchronize()
+    dev = (sd.cpu().numpy(), distributed.as_numpy_u32(face), distributed.as_numpy_u32(part), pt.cpu().numpy())
+    assert (dev[0] < 0).any() and (dev[0] > 0).any()
+
+    def check(got):
+        for a, b in zip(got, dev):
+            assert a.shape == b.shape and np.array_equal(a, b)
+
+    assert N.lib().msh_host_pool_trim() == 0  # a disabled pool still hands out a released block that fits
+    monkeypatch.setenv("MESH_AMD_PINNED_POOL_MB", "0")
+    staged = spatialsearch.aabbtree_signed_distance(t, q)
+    assert staged[0].base is None  # pool disabled: plain np.empty arrays
+    check(staged)
+    monkeypatch.setenv("MESH_AMD_HOST_REGISTER", "1")
+    check(spatialsearch.aabbtree_signed_distance(t, q))
+    monkeypatch.delenv("MESH_AMD_HOST_REGISTER")
+    monkeypatch.setenv("MESH_AMD_PINNED_POOL_MB", "1024")
+    pooled = spatialsearch.aabbtree_signed_distance(t, q)
+    owner = pooled[0]
+    while isinstance(owner, np.ndarray):
+        owner = owner.base
+    assert isinstance(owner, N._PinnedBlock)
+    check(pooled)
+    del pooled, owner
+    # the C entry point without part codes (the Python layer always asks for them)
+    sdist, hface, hpt = np.full(S, 7.0), np.full(S, 7, np.uint32), np.full((S, 3), 7.0)
+    N.check(N.lib().msh_tree_signed_distance(t.ptr, N.dptr(q), S, N.dptr(sdist), N.uptr(hface), None, N.dptr(hpt)))
+    check((sdist, hface, dev[2], hpt))
+    assert N.lib().msh_host_pool_trim() == 0
+
+
 # ---- 8. refusals ----
 def test_refusals(meshes):
     import torch

@@ -300,6 +300,42 @@ def test_determinism_and_layering(meshes):
     assert (w[ok] > 0.5).any() and (w[ok] < 0.5).any()
 
 
+def test_chunked_host_call_equals_device(meshes, monkeypatch):
+    """A host call above the 16 MB small-call limit runs the chunk pipeline: 600,000 rows on the golden sphere are
+    19.2 MB at 32 B per row, and MESH_AMD_HOST_CHUNK = 262144 makes three chunks, the last ragged.  At the default
+    beta the array equals msh_tree_winding_number_device on the same rows, with the result carved from the pinned pool
+    (downloaded in place) and with the pool off (staged)."""
+    import torch
+    from mesh_amd import _native as N, distributed, spatialsearch
+    v, f = golden(meshes, "sphere")
+    S = 600000
+    lo, hi = v.min(0), v.max(0)
+    q = np.random.default_rng(13).uniform(lo - 0.3 * (hi - lo), hi + 0.3 * (hi - lo), (S, 3))
+    assert 32 * S > 16 << 20
+    monkeypatch.setenv("MESH_AMD_HOST_CHUNK", "262144")
+    monkeypatch.setattr(N, "PINNED_MIN_BYTES", 1 << 20)
+    t = spatialsearch.aabbtree_compute(v, f)
+    d_w = torch.full((S,), -7.0, dtype=torch.float64, device="cuda:0")
+    distributed.winding_number_device(t, torch.from_numpy(q).to("cuda:0"), d_w)
+    torch.cuda.synchronize()
+    dev = d_w.cpu().numpy()
+    assert (dev > 0.5).any() and (dev < 0.5).any()
+    assert N.lib().msh_host_pool_trim() == 0  # a disabled pool still hands out a released block that fits
+    monkeypatch.setenv("MESH_AMD_PINNED_POOL_MB", "0")
+    staged = spatialsearch.aabbtree_winding_number(t, q)
+    assert staged.base is None  # pool disabled: a plain np.empty array
+    assert staged.shape == dev.shape and np.array_equal(staged, dev)
+    monkeypatch.setenv("MESH_AMD_PINNED_POOL_MB", "1024")
+    pooled = spatialsearch.aabbtree_winding_number(t, q)
+    owner = pooled
+    while isinstance(owner, np.ndarray):
+        owner = owner.base
+    assert isinstance(owner, N._PinnedBlock)
+    assert pooled.shape == dev.shape and np.array_equal(pooled, dev)
+    del pooled, owner
+    assert N.lib().msh_host_pool_trim() == 0
+
+
 def test_entry_cut_does_not_matter(case):
     from mesh_amd import spatialsearch
     v, f, q, _ = case("ellipsoid")
