@@ -362,9 +362,9 @@ def source_build_id(extra=""):
     import hashlib
     import os
     csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-    names = sorted(["sort.hip", "build.hip", "refine.hip", "nearest.hip", "rays.hip", "tritri.hip", "geometry.hip", "sign.hip",
-                    "winding.hip", "api.cpp", "devmem.cpp", "hostpipe.cpp", "entrycut.cpp", "blob.cpp",
-                    "hostpipe.h", "hostplan.h", "loaders.cpp", "common.h", "internal.h"])
+    names = sorted(["sort.hip", "build.hip", "refine.hip", "nearest.hip", "cutbuild.hip", "rays.hip", "tritri.hip", "geometry.hip",
+                    "sign.hip", "winding.hip", "api.cpp", "devmem.cpp", "hostpipe.cpp", "entrycut.cpp", "blob.cpp",
+                    "hostpipe.h", "hostplan.h", "loaders.cpp", "common.h", "internal.h", "knn.h"])
     h = hashlib.sha256()
     for p in [os.path.join(csrc, n) for n in names] + [os.path.join(csrc, "..", "..", "include", "meshsearch.h")]:
         with open(p, "rb") as fh:

@@ -588,4 +588,22 @@ __device__ inline unsigned xcd_remap(unsigned bid, unsigned nwg) {
     return base + (bid >> 3);
 }
 
+// Next 64-row tile of a persistent grid (the closest-point pass 1 and the ray kernels): 8 XCD-group counters, one 128-B
+// line each (counters[g * 32]), each owning a contiguous eighth of the ntiles tiles; a wave takes from its own group
+// first and steals from the others once it is exhausted.  ntiles: nothing is left.
+__device__ inline unsigned dequeue_tile(unsigned* counters, unsigned ntiles, unsigned group) {
+    for (unsigned k = 0; k < 8; ++k) {
+        const unsigned g = (group + k) & 7u;
+        const unsigned lo = (unsigned)(((unsigned long long)ntiles * g) >> 3);
+        const unsigned hi = (unsigned)(((unsigned long long)ntiles * (g + 1)) >> 3);
+        if (lo >= hi) continue;
+        if (__hip_atomic_load(&counters[g * 32], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= hi - lo) continue;
+        const unsigned t = atomicAdd(&counters[g * 32], 1u);
+        if (lo + t < hi) return lo + t;
+    }
+    return ntiles;
+}
+
+__device__ inline bool finite3(const D3& q) { return isfinite(q.x) && isfinite(q.y) && isfinite(q.z); }
+
 }  // namespace msh

@@ -371,6 +371,21 @@ int current_device(int* dev) {
     return MSH_OK;
 }
 
+// compute units of a device, looked up once per device (the persistent grids of the query launches are sized by it);
+// 256 where the runtime does not say
+int device_cus(int dev) {
+    static std::mutex mu;
+    static int cache[64] = {0};
+    std::lock_guard<std::mutex> g(mu);
+    if (dev < 0 || dev >= 64) return 256;
+    if (!cache[dev]) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        cache[dev] = n;
+    }
+    return cache[dev];
+}
+
 // End of an asynchronous batched build: wait for its last kernel, free its temporaries, read its GPU time.  A kernel
 // failure of the build surfaces here (MSH_EDEVICE), at the first call that needs the tree.
 int finish_pending(msh_tree* t) {

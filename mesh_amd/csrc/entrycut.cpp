@@ -9,7 +9,7 @@
 
 namespace msh {
 
-// Entry cut of a single triangle tree (nearest.hip cut_start / k_cut_build): a G^3 grid over the scene box
+// Entry cut of a single triangle tree (the walks' start: knn.h cut_start; the records: cutbuild.hip k_cut_level): a G^3 grid over the scene box
 // widened by 1/4 on every side (each axis at least 1/20 of the largest, so flat meshes get cells of a sane
 // shape), MSH_CUT_PER_LEAF cells per leaf up to 2^MSH_CUT_MAX_LOG2 cells (below; round 3 with leader phases:
 // G = 64 / 126 / 160: 1718 / 1742-1765 / 1782 M q/s against 1789-1800 at G = 200); the cell centres are answered
@@ -71,14 +71,14 @@ static int cut_grid(const msh_tree* t, bool fine) {
 }
 
 // The grid's cell centres are answered exactly by the tree (walks from the installed coarse grid when the fine one is
-// built, else from the root), then every cell is cut (nearest.hip k_cut_level): from the enclosing coarse cell's start
+// built, else from the root), then every cell is cut (cutbuild.hip k_cut_level): from the enclosing coarse cell's start
 // list when the coarse grid is installed and this grid is twice its resolution, else from the root.  C3 (round 6):
 // coarse grid 11 ms; fine grid from it 46 ms (centre walks 26, cut 18), 67 ms from the root
 // (profiles/r06_c3_cut_staged_ab.jsonl).  Round 6 also tried a pyramid -- the
 // coarsest grid answered exactly, each finer level cut from the coarser one's records with hints taken from the 8
 // coarse cells around it -- which built C3's grid in 41 ms instead of ~70 but started queries from worse hints:
 // 49.4 node visits per query against 42.5, 2.02-2.06 G q/s against 2.32-2.36 (profiles/r06_c3_cut_levels_ab.jsonl).
-// subdiv: the sub-cell depth of the directional drop, where the grid takes the drop at all (nearest.hip cut_dir_drop).
+// subdiv: the sub-cell depth of the directional drop, where the grid takes the drop at all (cutbuild.hip cut_dir_drop).
 static int build_entry_cut(msh_tree* t, bool fine, int subdiv) {
     const int G = cut_grid(t, fine);
     double half[3], H = 0.0, lo[3], w[3];

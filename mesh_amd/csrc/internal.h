@@ -240,12 +240,12 @@ int pack_tri_leaves(const double* d_v, const uint32_t* d_f, const uint32_t* d_or
 int pack_point_leaves(const double* d_v, const uint32_t* d_order, size_t P, PtRec* d_out, hipStream_t s);
 int point_bounds(const double* d_v, size_t P, double* d_lo, double* d_hi, hipStream_t s);
 
-// ---- queries (nearest.hip) ----
+// ---- query ordering (sort.hip) ----
 // 30-bit Morton codes of query points in the tree's scene box + iota values.
 int query_morton(const msh_tree* tree, const double* d_q, size_t S, uint32_t* keys, uint32_t* vals, hipStream_t s);
 // the box query Morton codes are taken in: the scene box widened by 10 % of its extent per side
 void query_box(const msh_tree* tree, float* lo, float* hi);
-// Query order (sort.hip): the S rows stably sorted by the top 30 - lo_bit bits (<= 24) of their Morton codes in the
+// Query order: the S rows stably sorted by the top 30 - lo_bit bits (<= 24) of their Morton codes in the
 // box lo..hi; the permutation (slot -> row) ends in ws.vals.  Uses ws.keys, ws.keys_alt, ws.vals_alt, ws.hist.
 int query_sort(const float* lo, const float* hi, const double* d_q, size_t S, int lo_bit, Workspace& ws, hipStream_t s);
 // slot i <- rows perm[i] of a (and b when non-null); inv[perm[i]] = i
@@ -254,14 +254,15 @@ int gather_rows(const double* d_a, const double* d_b, const uint32_t* d_perm, si
 // caller row j <- slot inv[j] (record fields + nw doubles per row from d_w)
 int unpermute_results(const QRes* d_res, const double* d_w, int nw, const uint32_t* d_inv, size_t S, const SlotOut& o,
                       hipStream_t s);
-// Entry cut of a single triangle tree (nearest.hip k_cut_level): the records of a G^3 grid from the cell centres' exact
+// ---- entry cut, build time (cutbuild.hip) ----
+// Entry cut of a single triangle tree (k_cut_level): the records of a G^3 grid from the cell centres' exact
 // answers (closest points d_pts, their leaves d_hint); e4: 32-B records of 4-B entries (trees of <= 2^20 leaves), else 64-B records.
 // kCutK start entries per cell (the hint takes the record's eighth word; round 5: 8 entries of 8 B + a separate hint;
 // 4 entries: 1773-1800 M q/s against 8, 16: 1285, C3, profiles/r03_c3_entry_cut_ab.jsonl)
 constexpr int kCutK = 7;
 constexpr uint32_t kCutEmpty = 0x7FFFFFFFu;  // empty 64-B record entry: not a node id (ids < T - 1 <= 2^31 - 2) nor a ~leaf
 constexpr size_t kEnt4MaxLeaves = (size_t)1 << 20;  // 4-B stack / cut entries: refs in [-2^20, 2^20), 21 bits
-// k_cut_level's directional drop (nearest.hip cut_dir_drop) and the mark of a record it shortened: bit 30 of word 0
+// k_cut_level's directional drop (cutbuild.hip cut_dir_drop) and the mark of a record it shortened: bit 30 of word 0
 // (the hint leaf; leaves < 2^26) in 32-B records -- 64-B records zero their radius word instead.  The alongnormal
 // walks start at the root in a marked cell (rays.hip); the closest-point walks mask the bit.
 constexpr uint32_t kCutDirFlag = 0x40000000u;
@@ -284,6 +285,7 @@ int points_from_faces(const msh_tree* tree, const uint32_t* d_inv, const double*
                       uint32_t* d_part, double* d_pt, hipStream_t s);
 // d_hint[cell] = the leaf holding face d_face[cell] (d_inv: T scratch words)
 int cut_hints(const msh_tree* tree, const uint32_t* d_face, size_t n, uint32_t* d_inv, int* d_hint, hipStream_t s);
+// ---- closest-point queries (nearest.hip) ----
 // closest point: o.face, o.part (nullable), o.pt; with o.w (3 per row) the barycentric variant (part unused)
 int launch_nearest(const msh_tree* tree, const QueryOrder& ord, size_t S, const SlotOut& o, hipStream_t s);
 // batched trees: n = (meshes) * S queries, slot i answered on mesh mesh0 + i / S (the batched sort is mesh-major)
@@ -407,6 +409,7 @@ extern thread_local int g_device;               // msh_set_device (-1: the runti
 extern thread_local std::vector<int> g_devices;  // devices of the trees built next on this thread (msh_set_devices)
 int use_device(int dev);
 int current_device(int* dev);
+int device_cus(int dev);  // compute units of a device (cached; 256 when unknown): sizes the persistent grids
 // query workspaces handed from a freed triangle tree to the next one built on the device (devmem.cpp WsPool)
 void ws_pool_take(int dev, Workspace& ws);
 size_t ws_pool_trim();

@@ -235,10 +235,8 @@ constexpr int kAlongStack = MSH_ALONG_STACK;
 // A lane pends at most one leaf: its bound is never stale (the wave leaf list, which lets lanes walk on with up to
 // N leaves waiting, walked 34.4 nodes per ray instead of 29.5 at N >= 4; at N = 1 it ran 4.75 ms against
 // 5.02 for per-lane tests, profiles/r06_c5_along_list_pend_ab.jsonl, and this form needs neither its LDS ring nor the
-// owners' rows fetched by ds_bpermute).  The list variant (traverse_along_list) was removed: it never learned the
-// entry cut (capf was not reset and no walk restarted from the root, so wrong answers on a tree that holds one) and
-// it used the default stack depth, overrunning LDS at MSH_ALONG_STACK < 16.
-// Each next node is loaded into the lane's LDS slot as soon as it is chosen (node_prefetch, as k_knn's list path), so
+// owners' rows fetched by ds_bpermute).  The list variant (MSH_ALONG_LIST, traverse_along_list) is retired.
+// Each next node is loaded into the lane's LDS slot as soon as it is chosen (node_prefetch, as k_knn_list), so
 // its latency overlaps the wave's leaf phases and the loop's bookkeeping.
 // rec / rho (round 6): the ray's cell of the closest-point entry cut and the radius around p its start list covers (every
 // subtree left out of it is farther than rho from p: k_rays).  The walk first runs from the list with the bound capped
@@ -425,21 +423,6 @@ struct RayArgs {
     double cut_r;  // the cells' half-diagonal as the cut's build took it, rounded down
 };
 
-__device__ inline unsigned dequeue_tile_r(unsigned* counters, unsigned ntiles, unsigned group) {
-    for (unsigned k = 0; k < 8; ++k) {
-        const unsigned g = (group + k) & 7u;
-        const unsigned lo = (unsigned)(((unsigned long long)ntiles * g) >> 3);
-        const unsigned hi = (unsigned)(((unsigned long long)ntiles * (g + 1)) >> 3);
-        if (lo >= hi) continue;
-        if (__hip_atomic_load(&counters[g * 32], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= hi - lo) continue;
-        const unsigned t = atomicAdd(&counters[g * 32], 1u);
-        if (lo + t < hi) return lo + t;
-    }
-    return ntiles;
-}
-
-__device__ inline bool finite_d3(const D3& x) { return isfinite(x.x) && isfinite(x.y) && isfinite(x.z); }
-
 // waves per SIMD: visibility 4 (127 VGPRs, no spills); alongnormal 3 (168 VGPRs, 48 KB of LDS per block with the node
 // slots; at 4 the per-lane fp64 leaf test spilled 37 VGPRs: C5 7.41 vs 6.62 ms in round 2, 5.74 vs 4.98 ms in round 6
 // before the postponed leaf tests, profiles/r06_c5_along_ab.jsonl)
@@ -467,7 +450,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MODE == 
     unsigned nxt = ~0u;
     for (;;) {
         unsigned tile = 0;
-        if (lane == 0) tile = (nxt != ~0u && glo + nxt < ghi) ? glo + nxt : dequeue_tile_r(a.counters, a.ntiles, group);
+        if (lane == 0) tile = (nxt != ~0u && glo + nxt < ghi) ? glo + nxt : dequeue_tile(a.counters, a.ntiles, group);
         tile = __shfl(tile, 0);
         if (tile >= a.ntiles) break;
         const size_t i = (size_t)tile * 64 + lane;
@@ -481,7 +464,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MODE == 
             const D3 n = live ? D3{a.n[3 * ri], a.n[3 * ri + 1], a.n[3 * ri + 2]} : D3{0.0, 0.0, 1.0};
             const D3 dp = ray_dir(p, n), pr = vsub(p, org);
             AlongPol pol{a.tris, p, n, make_rayf(pr, dp, a.M, true), INFINITY, MSH_NO_FACE, -1, INFINITY, INFINITY};
-            const bool go = live && finite_d3(p) && finite_d3(dp);
+            const bool go = live && finite3(p) && finite3(dp);
             // the entry cut's cell of p: its start list covers every face within rho of p, rho = R - |p - c| with R
             // the radius the build kept around the centre c (64-B records hold it; else d(c) + 2r, d(c): c's distance
             // to its hint face, the face the build found closest to c); both rounded down
@@ -544,7 +527,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MODE == 
             const D3 src = vadd(vv, vscale(a.min_dist, dir));
             const D3 d = ray_dir(src, dir);
             AnyPol pol{a.tris, src, d, make_rayf(vsub(src, org), d, a.M, false), false};
-            if (finite_d3(src) && finite_d3(d))
+            if (finite3(src) && finite3(d))
                 traverse_rays<AnyPol, STATS>(a.nodes, a.T, pol, lds, spill, n_nodes, n_leaves);
             if (STATS) continue;
             const uint32_t reach = pol.hit ? 0u : 1u;
@@ -573,12 +556,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MODE == 
     }
 }
 
-static int device_cus_r(int dev) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-}
-
 template <int MODE, bool STATS>
 static int launch_rays(msh_tree* tree, RayArgs a, size_t nrays, hipStream_t s, const char* timer) {
     if (nrays == 0) return MSH_OK;
@@ -590,7 +567,7 @@ static int launch_rays(msh_tree* tree, RayArgs a, size_t nrays, hipStream_t s, c
     for (int k = 0; k < 3; ++k) a.org[k] = tree->origin[k];
     a.M = tree->half_diag;
     a.ntiles = (unsigned)((nrays + 63) / 64);
-    const unsigned nblk = std::min<unsigned>((a.ntiles + 3) / 4, (unsigned)device_cus_r(tree->device) * 5u);
+    const unsigned nblk = std::min<unsigned>((a.ntiles + 3) / 4, (unsigned)device_cus(tree->device) * 5u);
     MSH_TRY(tree->ws.counters.reserve(9 * 32 * sizeof(unsigned)));
     a.counters = tree->ws.counters.as<unsigned>();
     MSH_HIP(hipMemsetAsync(a.counters, 0, 8 * 32 * sizeof(unsigned), s));

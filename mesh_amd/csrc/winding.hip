@@ -300,12 +300,6 @@ __global__ __launch_bounds__(kBlock) void k_winding(WindArgs a) {
     }
 }
 
-static int device_cus_w(int dev) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-}
-
 template <bool STATS>
 static int launch_wind(msh_tree* tree, const void* table, const QueryOrder& ord, size_t S, double beta, double* d_w,
                        unsigned long long* d_stats, hipStream_t s) {
@@ -323,7 +317,7 @@ static int launch_wind(msh_tree* tree, const void* table, const QueryOrder& ord,
     a.stats = d_stats;
     for (int k = 0; k < 3; ++k) a.org[k] = tree->origin[k];
     // persistent grid: 8 blocks per CU at most (8 KB of LDS each), every wave strides over the tiles
-    const unsigned nb = std::min<unsigned>((unsigned)((S + kBlock - 1) / kBlock), (unsigned)device_cus_w(tree->device) * 8u);
+    const unsigned nb = std::min<unsigned>((unsigned)((S + kBlock - 1) / kBlock), (unsigned)device_cus(tree->device) * 8u);
     const int need = tree->max_depth + 1;
     a.cap = kWindStack;
     if (need > kWindStack) {

@@ -47,7 +47,7 @@ def pmc_of(target, kernel, units):
 
 # pass 1 of the closest-point traversal: the lean kernel of cut-started sorted launches and the generic one, then
 # their names in profiles taken while the lean kernel was an instantiation of k_knn
-PASS1_KERNELS = ("msh::k_knn_lean<0>", "msh::k_knn<0, false, true, true>",
+PASS1_KERNELS = ("msh::k_knn_lean<0>", "msh::k_knn_list<0, false, true>", "msh::k_knn<0, false, true, true>",
                  "msh::k_knn<0, false, true, true, true>", "msh::k_knn<0, false, true, true, false>")
 
 

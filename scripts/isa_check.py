@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Register-pressure check of the closest-point traversal kernels (CPU only, no GPU needed).
 
-Compiles mesh_amd/csrc/nearest.hip to gfx950 assembly (optionally with extra -D flags) and reports, for k_knn_lean<MODE>
-and k_knn<MODE, false, LIST, PF> (MODE 0 and 3), the register and spill counts of the code object's metadata, and what
+Compiles mesh_amd/csrc/nearest.hip to gfx950 assembly (optionally with extra -D flags) and reports, for k_knn_lean<MODE>,
+k_knn_list<MODE, false, PF> and k_knn_queue<MODE, false> (MODE 0 and 3), the register and spill counts of the code object's metadata, and what
 sits inside the tile's wave loop (found from LLVM's loop annotations as the parent of the loop with the fp64 construction): scratch (VGPR spill) instructions,
 lane reads and writes (v_readlane / v_writelane: SGPR spill traffic), and the static VALU / SALU / branch counts, split
 into the leaf rounds (the innermost loop that holds the fp64 construction) and the node step (the rest of the wave
@@ -14,18 +14,21 @@ reloads, so a variant with loop spills is not worth a GPU session.
 --save FILE only writes the assembly; --diff FILE (the --save of another tree) compares the two kernel by kernel instead
 of reporting -- the .amdhsa_* block and the instruction text, comments dropped and labels renumbered -- and exits 1
 when any kernel differs.  Two compiles of one source differ only in the __hip_cuid_* symbol, so a refactor that should
-not touch the generated code shows "identical" for every kernel.  Both take --src FILE, the source of mesh_amd/csrc to
-compile (default nearest.hip; the report is of nearest.hip's kernels only).  A tree from before these options gets a
-copy of this script first (it compiles the sources beside it):
+not touch the generated code shows "identical" for every kernel.  Both take --src FILE, a source of mesh_amd/csrc to
+compile (default nearest.hip; the report is of nearest.hip's kernels only), any number of times, or --src all for every
+.hip file: the kernels of all of them are compared by name, so code may move between files (knn.h's users, cutbuild.hip
+and sort.hip hold what nearest.hip held); a kernel renamed by a split is found through pre_split().  A tree from before
+these options gets a copy of this script first (it compiles the sources beside it):
 
-    cp scripts/isa_check.py ../parent/scripts/ && python ../parent/scripts/isa_check.py --src rays.hip --save /tmp/parent.s
-    python scripts/isa_check.py --src rays.hip --diff /tmp/parent.s
+    cp scripts/isa_check.py ../parent/scripts/ && python ../parent/scripts/isa_check.py --src all --save /tmp/parent.s
+    python scripts/isa_check.py --src all --diff /tmp/parent.s
 """
 import os
 import re
 import subprocess
 import sys
 import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(R, "mesh_amd", "csrc")
@@ -167,15 +170,18 @@ def kernels(s):
 
 
 def pre_split(name):
-    """k_knn<MODE, STATS, LIST, PF, LEAN> of an assembly from before k_knn_lean was a kernel of its own, under the name
-    it has now"""
-    m = re.fullmatch(r"_ZN3msh5k_knnILi(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)EEEvNS_7KnnArgsE", name)
+    """A pass-1 kernel of an assembly from before k_knn was split, under the name it has now: k_knn<MODE, STATS, LIST, PF,
+    LEAN> (before k_knn_lean was a kernel of its own) and k_knn<MODE, STATS, LIST, PF> (before the list and the queue
+    path were)"""
+    m = re.fullmatch(r"_ZN3msh5k_knnILi(\d)ELb(\d)ELb(\d)ELb(\d)(?:ELb(\d))?EEEvNS_7KnnArgsE", name)
     if not m:
         return name
     mode, stats, lst, pf, lean = m.groups()
     if lean == "1":
         return f"_ZN3msh10k_knn_leanILi{mode}EEEvNS_7KnnArgsE"
-    return f"_ZN3msh5k_knnILi{mode}ELb{stats}ELb{lst}ELb{pf}EEEvNS_7KnnArgsE"
+    if lst == "1":
+        return f"_ZN3msh10k_knn_listILi{mode}ELb{stats}ELb{pf}EEEvNS_7KnnArgsE"
+    return f"_ZN3msh11k_knn_queueILi{mode}ELb{stats}EEEvNS_7KnnArgsE"
 
 
 def diff(s, other):
@@ -202,19 +208,23 @@ def diff(s, other):
 def main():
     flags = sys.argv[1:]
     save = other = None
-    src = "nearest.hip"
-    if "--src" in flags:  # with --save / --diff: another source of mesh_amd/csrc
-        src = os.path.basename(flags.pop(flags.index("--src") + 1))
+    srcs = []
+    while "--src" in flags:  # with --save / --diff: other sources of mesh_amd/csrc, or `all` for every .hip
+        srcs.append(os.path.basename(flags.pop(flags.index("--src") + 1)))
         flags.remove("--src")
-        if src != "nearest.hip" and "--save" not in flags and "--diff" not in flags:
-            sys.exit("--src goes with --save or --diff: the report is of nearest.hip's kernels")
+    if srcs and srcs != ["nearest.hip"] and "--save" not in flags and "--diff" not in flags:
+        sys.exit("--src goes with --save or --diff: the report is of nearest.hip's kernels")
+    if "all" in srcs:
+        srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
+    srcs = srcs or ["nearest.hip"]
     if "--save" in flags:  # keep the assembly, for another tree's --diff
         save = flags.pop(flags.index("--save") + 1)
         flags.remove("--save")
     if "--diff" in flags:
         other = flags.pop(flags.index("--diff") + 1)
         flags.remove("--diff")
-    s = compile_asm(flags, src)
+    with ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:  # kernel names are unique across the library
+        s = "\n".join(ex.map(lambda f: compile_asm(flags, f), srcs))
     if save:
         with open(save, "w") as f:
             f.write(s)
@@ -224,10 +234,12 @@ def main():
         sys.exit(diff(s, other))
     for mode in (0, 3):
         print(report(s, f"_ZN3msh10k_knn_leanILi{mode}EEEvNS_7KnnArgsE", dict(kernel="k_knn_lean", mode=mode)))
-    for lst, pf in ((True, True), (True, False), (False, False)):
+    for pf in (True, False):
         for mode in (0, 3):
-            print(report(s, f"_ZN3msh5k_knnILi{mode}ELb0ELb{int(lst)}ELb{int(pf)}EEEvNS_7KnnArgsE",
-                         dict(kernel="k_knn", mode=mode, list=lst, prefetch=pf)))
+            print(report(s, f"_ZN3msh10k_knn_listILi{mode}ELb0ELb{int(pf)}EEEvNS_7KnnArgsE",
+                         dict(kernel="k_knn_list", mode=mode, prefetch=pf)))
+    for mode in (0, 3):
+        print(report(s, f"_ZN3msh11k_knn_queueILi{mode}ELb0EEEvNS_7KnnArgsE", dict(kernel="k_knn_queue", mode=mode)))
 
 
 if __name__ == "__main__":

@@ -9,7 +9,7 @@ import sys
 
 # pass 1: the lean kernel of cut-started sorted launches and the generic one (then their names while the lean kernel
 # was an instantiation of k_knn); pass 2
-TRAVERSAL = ("k_knn_lean<0>", "k_knn<0, false, true, true>", "k_knn<0, false, true, true, true>",
+TRAVERSAL = ("k_knn_lean<0>", "k_knn_list<0, false, true>", "k_knn<0, false, true, true>", "k_knn<0, false, true, true, true>",
              "k_knn<0, false, true, true, false>", "k_knn_coop<0, false>")
 
 con = sqlite3.connect(sys.argv[1])

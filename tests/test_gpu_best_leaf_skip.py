@@ -1,4 +1,4 @@
-"""A walk does not queue the leaf its query has already evaluated (nearest.hip WalkerT::step_list / step_collect).
+"""A walk does not queue the leaf its query has already evaluated (knn.h WalkerT::step_list / step_collect).
 
 A leaf that was evaluated for the query before the walk reaches it -- the cell's hint leaf in the lean kernel, the
 query's best leaf in the generic ones -- is dropped there, so its second exact construction never runs.  That

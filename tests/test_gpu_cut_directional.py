@@ -1,4 +1,4 @@
-"""The entry cut's directional drop (nearest.hip k_cut_level / cut_dir_drop) changes no answer.
+"""The entry cut's directional drop (cutbuild.hip k_cut_level / cut_dir_drop) changes no answer.
 
 Walks that start from a cut built with the directional rule give the arrays of walks from the root, bit for bit, on
 the closest-point path (lean and generic kernels, 32-B and 64-B records, grids whose cell half-diagonal r runs from

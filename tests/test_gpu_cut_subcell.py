@@ -1,4 +1,4 @@
-"""The directional drop proved on sub-cells (nearest.hip cut_dir_drop, depth MESH_AMD_CUT_SUBDIV = 0 / 1 / 2) changes no
+"""The directional drop proved on sub-cells (cutbuild.hip cut_dir_drop, depth MESH_AMD_CUT_SUBDIV = 0 / 1 / 2) changes no
 answer.
 
 As tests/test_gpu_cut_directional.py: walks without a cut (set_entry_cut(0)) are the reference, and walks from a cut

@@ -759,7 +759,7 @@ std::vector<int> cell_cut(const ObbTree& t, const double* c, double lim, int dcu
     }
     return cur;
 }
-// the directional drop of nearest.hip k_cut_level: with pc the closest point of the centre c, d_p = |c - pc|, d_B the
+// the directional drop of cutbuild.hip k_cut_level: with pc the closest point of the centre c, d_p = |c - pc|, d_B the
 // distance from c to the box and u_B, u_p the unit vectors from the box's nearest point and from pc to c, every q
 // within r of c has dist(q, B) - |q - pc| >= d_B - d_p - r (|u_B - u_p| + 4 r / d_B + 2 r / d_p)
 bool dir_drop(const double* c, const double* pc, double r, const OBB& o) {
@@ -777,7 +777,7 @@ bool dir_drop(const double* c, const double* pc, double r, const OBB& o) {
     for (int k = 0; k < 3; ++k) du += (g[k] / dB - e[k] / dp) * (g[k] / dB - e[k] / dp);
     return dB - dp - r * (std::sqrt(du) + 4 * r / dB + 2 * r / dp) > 1e-9 * (dB + dp);
 }
-// dir_drop as nearest.hip cut_dir_drop applies it with sub-cells: the whole cell (centre c, radius r, half-widths hw)
+// dir_drop as cutbuild.hip cut_dir_drop applies it with sub-cells: the whole cell (centre c, radius r, half-widths hw)
 // first; on failure each of its 8 octants (centres c +- hw / 2, radius r / 2) must prove the drop, with the same pc,
 // and an octant that fails is split once more (radius r / 4) when subdiv is 2.  subdiv 0: the whole cell only.
 // evals (nullable): += the rule evaluations spent.
