@@ -88,8 +88,8 @@ int msh_set_device(int device);
  * Mesh.closest_faces_and_points -> AabbTree.nearest, mesh.py:454-455 / search.py:26-30, has no device argument).
  * Trees built afterwards on the calling thread are built on the first device and replicated to the others
  * (blob pack + peer copy + unpack); the host-buffer entry points (msh_tree_nearest, _nearest_bary, _signed_distance,
- * _nearest_alongnormal, msh_ntree_nearest, msh_points_nearest: contiguous row ranges; msh_visibility: camera
- * ranges) then split their rows over the devices, one host thread and one chunk pipeline per device, so each
+ * _nearest_alongnormal, _knearest, msh_ntree_nearest, msh_points_nearest, msh_points_knearest: contiguous row ranges;
+ * msh_visibility: camera ranges) then split their rows over the devices, one host thread and one chunk pipeline per device, so each
  * device's host link carries its share.  Calls below 32 MB of rows stay on the first device.  The answers equal
  * the one-device answers bit for bit (disjoint row ranges of the same arrays).  *_device entry points, batched
  * trees and the intersection tests stay on the handle's own device.  Untested across devices: the GPU box this
@@ -387,6 +387,42 @@ int msh_batch_nearest_bary_device(msh_tree* tree, const double* d_q, size_t S, u
 int msh_points_build(const double* v, size_t P, msh_tree** out);
 /* nearest vertex: lexicographic min (squared distance, vertex index); dist = sqrt(d2) */
 int msh_points_nearest(msh_tree* tree, const double* q, size_t S, uint32_t* idx, double* dist);
+
+/* ---- K-nearest and radius-capped queries on point trees and plain triangle trees ----
+ * For row i and a tree of n primitives (the vertices of a point tree; the leaf triangles of a triangle tree, the extra
+ * faces of msh_tree_build_ex included, with the ids the pair lists use), the answer is the first min(K, m_i) of the
+ * primitives with d2 <= r2, ascending by the lexicographic key (d2, id):
+ *   d2   the exact fp64 squared distance the 1-NN entry points compute ((dx dx + dy dy) + dz dz to a vertex; CGAL's
+ *        closest-point construction on a triangle), id the vertex index or face id;
+ *   r2   r_max * r_max, rounded once in fp64; r_max = +inf: no cap; r_max = 0: exact hits only;
+ *   m_i  the number of primitives that qualify.
+ * A row's answer is a function of (tree, q_i, K, r_max) alone -- not of the visit order, the other rows, the chunking
+ * or the device split; ties on d2 are decided by id; no atomic decides content or order.  dist[i, j] = sqrt(d2).
+ * Unused entries j >= count[i] hold MSH_NO_FACE, +inf, a NaN point and part 0; a row with a non-finite coordinate
+ * gets count 0 and padding only.  Column 0 of an uncapped answer equals msh_points_nearest (idx, dist) and
+ * msh_tree_nearest (face, part, point) bit for bit, and columns 0..K-1 of a K' > K answer equal the K answer.
+ * 1 <= K <= MSH_KNEAREST_MAX and r_max >= 0 (not NaN), else MSH_EINVAL -- checked before the handle, then the handle,
+ * then the pointers.  S == 0 returns MSH_OK; K > n is legal (padding); a tree of one primitive works.
+ * msh_points_* take point trees, msh_tree_knearest* plain triangle trees; normals-metric and batched trees and NULL
+ * handles are MSH_EINVAL.  The walk starts at the root (the entry cut is neither built nor used), one lane per row in
+ * the closest-point path's slot order, depth first, nearer child first, keeping a sorted list of at most K entries and
+ * pruning on its K-th.  The host entry points go through the pinned-slab pipeline and split their
+ * rows over the handle's replicas; the *_device ones take device pointers and are asynchronous on `stream` -- except
+ * the first msh_tree_knearest_device call with pt or part on a handle, which builds the face -> leaf map and waits
+ * for it (as msh_tree_points_from_faces_device does).  count, pt and part may be NULL.
+ * msh_timing_get names: "kbest" (the walk), "kbest_finish" (the pass that writes dist, pt, part and the padding). */
+#define MSH_KNEAREST_MAX 64
+int msh_points_knearest(msh_tree* tree, const double* q, size_t S, uint32_t K, double r_max, uint32_t* idx,
+                        double* dist, uint32_t* count);
+int msh_points_knearest_device(msh_tree* tree, const double* d_q, size_t S, uint32_t K, double r_max, uint32_t* d_idx,
+                               double* d_dist, uint32_t* d_count, void* stream);
+int msh_tree_knearest(msh_tree* tree, const double* q, size_t S, uint32_t K, double r_max, uint32_t* face, double* dist,
+                      double* pt, uint32_t* part, uint32_t* count);
+int msh_tree_knearest_device(msh_tree* tree, const double* d_q, size_t S, uint32_t K, double r_max, uint32_t* d_face,
+                             double* d_dist, double* d_pt, uint32_t* d_part, uint32_t* d_count, void* stream);
+/* untimed, same walk, point trees and plain triangle trees: counts[0] nodes visited, [1] primitives evaluated,
+ * [2] list insertions, [3] deepest stack any row reached (entries).  d_q is a device pointer; synchronous. */
+int msh_tree_knearest_stats(msh_tree* tree, const double* d_q, size_t S, uint32_t K, double r_max, uint64_t counts[4]);
 
 /* ---- multi-GPU replication (RCCL broadcast of a built BVH over xGMI) ---- */
 /* Size of the flat device blob holding the mesh + BVH of a handle. */

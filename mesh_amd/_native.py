@@ -80,6 +80,13 @@ SIGNATURES = [
     ("msh_vertex_normals_device", _i, [_vp, _sz, _vp, _sz, _vp, _vp]),
     ("msh_points_build", _i, [_c_double_p, _sz, ctypes.POINTER(_vp)]),
     ("msh_points_nearest", _i, [_vp, _c_double_p, _sz, _c_u32_p, _c_double_p]),
+    ("msh_points_knearest", _i, [_vp, _c_double_p, _sz, ctypes.c_uint32, ctypes.c_double, _c_u32_p, _c_double_p,
+                                 _c_u32_p]),
+    ("msh_points_knearest_device", _i, [_vp, _vp, _sz, ctypes.c_uint32, ctypes.c_double, _vp, _vp, _vp, _vp]),
+    ("msh_tree_knearest", _i, [_vp, _c_double_p, _sz, ctypes.c_uint32, ctypes.c_double, _c_u32_p, _c_double_p,
+                               _c_double_p, _c_u32_p, _c_u32_p]),
+    ("msh_tree_knearest_device", _i, [_vp, _vp, _sz, ctypes.c_uint32, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("msh_tree_knearest_stats", _i, [_vp, _vp, _sz, ctypes.c_uint32, ctypes.c_double, _c_u64_p]),
     ("msh_tree_blob_size", _i, [_vp, ctypes.POINTER(_sz)]),
     ("msh_tree_blob_pack", _i, [_vp, _vp, _vp]),
     ("msh_tree_blob_unpack", _i, [_vp, _sz, _i, _vp, ctypes.POINTER(_vp)]),
@@ -144,6 +151,20 @@ class WindingInfo(ctypes.Structure):
 
 # MSH_WINDING_BETA_DEFAULT (include/meshsearch.h; tests/test_winding_host.py checks that the two agree)
 WINDING_BETA_DEFAULT = 4.0
+
+# MSH_KNEAREST_MAX (include/meshsearch.h; tests/test_knearest_host.py checks that the two agree)
+KNEAREST_MAX = 64
+
+
+def check_knearest(k, max_distance, what):
+    """(k, r_max) of a K-nearest call as the C ABI takes them; ValueError for k outside 1..KNEAREST_MAX or a negative
+    or NaN cap, before any device work."""
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= KNEAREST_MAX:
+        raise ValueError("%s: k must be an integer in 1..%d, got %r" % (what, KNEAREST_MAX, k))
+    r = float(max_distance)
+    if not r >= 0.0:
+        raise ValueError("%s: the distance cap must be >= 0 (inf: none), got %r" % (what, max_distance))
+    return int(k), r
 
 
 def _preload_single_hip_runtime():
@@ -337,6 +358,14 @@ class Handle(object):
                                            WINDING_BETA_DEFAULT if beta is None else float(beta), out))
         return tuple(int(x) for x in out)
 
+    def knearest_stats(self, d_q, S, k, max_distance=float("inf")):
+        """msh_tree_knearest_stats on S device rows at address d_q (point and plain triangle trees) -> (nodes visited,
+        primitives evaluated, list insertions, deepest stack any row reached); untimed, the same walk as the query."""
+        k, r = check_knearest(k, max_distance, "knearest_stats")
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().msh_tree_knearest_stats(self.ptr, _vp(d_q), int(S), k, r, out))
+        return tuple(int(x) for x in out)
+
     def free(self):
         if self.ptr:
             lib().msh_tree_free(self.ptr)
@@ -363,7 +392,7 @@ def source_build_id(extra=""):
     import os
     csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
     names = sorted(["sort.hip", "build.hip", "refine.hip", "nearest.hip", "cutbuild.hip", "rays.hip", "tritri.hip", "geometry.hip",
-                    "sign.hip", "winding.hip", "api.cpp", "devmem.cpp", "hostpipe.cpp", "entrycut.cpp", "blob.cpp",
+                    "sign.hip", "winding.hip", "kbest.hip", "api.cpp", "devmem.cpp", "hostpipe.cpp", "entrycut.cpp", "blob.cpp",
                     "hostpipe.h", "hostplan.h", "loaders.cpp", "common.h", "internal.h", "knn.h"])
     h = hashlib.sha256()
     for p in [os.path.join(csrc, n) for n in names] + [os.path.join(csrc, "..", "..", "include", "meshsearch.h")]:

@@ -180,6 +180,23 @@ static int check_batch(const msh_tree* t, const char* fn) {
 
 static hipStream_t pick(msh_tree* t, void* stream) { return stream ? static_cast<hipStream_t>(stream) : t->stream; }
 
+// the handle's face -> leaf map (msh_tree_points_from_faces_device, msh_tree_knearest*), built on first use; that
+// call waits for it, so the map is complete before any stream reads it
+static int ensure_face_leaf(msh_tree* t, hipStream_t s) {
+    if (t->d_face_leaf) return MSH_OK;
+    uint32_t* inv = nullptr;
+    MSH_HIP(dmalloc(&inv, t->T * sizeof(uint32_t)));
+    const int st = face_leaf_map(t, inv, s);
+    if (st != MSH_OK) {
+        (void)hipStreamSynchronize(s);
+        (void)dfree(inv);
+        return st;
+    }
+    MSH_HIP(hipStreamSynchronize(s));
+    t->d_face_leaf = inv;
+    return MSH_OK;
+}
+
 // An instrumented launch on the handle's own stream: the rows' slot order (d_q == nullptr: the launch takes none),
 // `zeroed` counter words of ws.stats cleared, launch(ord, d_counts, s), the first `nread` words read back into h.
 template <class Launch>
@@ -571,18 +588,7 @@ int msh_tree_points_from_faces_device(msh_tree* t, const double* d_q, size_t S, 
     if (S == 0) return MSH_OK;
     if (!d_q || !d_face || !d_pt) { set_error("msh_tree_points_from_faces_device: null argument"); return MSH_EINVAL; }
     hipStream_t s = pick(t, stream);
-    if (!t->d_face_leaf) {
-        uint32_t* inv = nullptr;
-        MSH_HIP(dmalloc(&inv, t->T * sizeof(uint32_t)));
-        const int st = face_leaf_map(t, inv, s);
-        if (st != MSH_OK) {
-            (void)hipStreamSynchronize(s);
-            (void)dfree(inv);
-            return st;
-        }
-        MSH_HIP(hipStreamSynchronize(s));  // the map is complete before any stream reads it
-        t->d_face_leaf = inv;
-    }
+    MSH_TRY(ensure_face_leaf(t, s));
     // no workspace is used (tree leaves and the map only), so no WsOrder: a rebuild of other ranks' points on a side
     // stream overlaps the next batch's traversal
     return points_from_faces(t, t->d_face_leaf, d_q, S, d_face, d_part, d_pt, s);
@@ -1229,6 +1235,116 @@ int msh_points_nearest(msh_tree* t, const double* q, size_t S, uint32_t* idx, do
         MSH_TRY(sort_queries(h, d[cq], nullptr, rows, s, &ord));
         return launch_points_nearest(h, ord, rows, SlotOut{d[cidx], nullptr, nullptr, d[cdist], nullptr}, s);
     });
+}
+
+// ---- K-nearest and radius-capped queries (kbest.hip) ----
+static int check_kbest_args(uint32_t K, double r_max, const char* fn) {
+    if (K < 1 || K > MSH_KNEAREST_MAX) {
+        set_error("%s: K must be in 1..%d, got %u", fn, MSH_KNEAREST_MAX, K);
+        return MSH_EINVAL;
+    }
+    if (!(r_max >= 0.0)) {
+        set_error("%s: r_max must be >= 0 (+inf: no cap), got %g", fn, r_max);
+        return MSH_EINVAL;
+    }
+    return MSH_OK;
+}
+
+// point trees (want kPoints) or plain triangle trees (want kTriangles)
+static int check_kbest_tree(const msh_tree* t, int want, const char* fn) {
+    MSH_TRY(check_tree(t, want, fn));
+    if (t->kind == kNormals) {
+        set_error("%s: normals-metric tree handle (K-nearest queries need a plain triangle tree)", fn);
+        return MSH_EINVAL;
+    }
+    return MSH_OK;
+}
+
+// one launch over d_q in the closest-point path's slot order, from the root (no entry cut)
+static int kbest_run(msh_tree* t, const double* d_q, size_t S, uint32_t K, double r_max, const KbOut& o, hipStream_t s) {
+    const bool rebuild = t->kind == kTriangles && (o.pt || o.part);  // points and parts go through the face's leaf
+    if (rebuild) MSH_TRY(ensure_face_leaf(t, s));
+    WsOrder order(t, s);
+    QueryOrder ord;
+    MSH_TRY(sort_queries(t, d_q, nullptr, S, s, &ord, true));
+    return launch_kbest(t, ord, S, K, r_max, o, rebuild ? t->d_face_leaf : nullptr, s);
+}
+
+int msh_points_knearest_device(msh_tree* t, const double* d_q, size_t S, uint32_t K, double r_max, uint32_t* d_idx,
+                               double* d_dist, uint32_t* d_count, void* stream) {
+    MSH_TRY(check_kbest_args(K, r_max, "msh_points_knearest_device"));  // before the handle, as winding's beta
+    MSH_TRY(check_kbest_tree(t, kPoints, "msh_points_knearest_device"));
+    MSH_TRY(check_count(S, "msh_points_knearest_device"));
+    if (S == 0) return MSH_OK;
+    if (!d_q || !d_idx || !d_dist) { set_error("msh_points_knearest_device: null argument"); return MSH_EINVAL; }
+    return kbest_run(t, d_q, S, K, r_max, KbOut{d_idx, d_dist, nullptr, nullptr, d_count}, pick(t, stream));
+}
+
+int msh_points_knearest(msh_tree* t, const double* q, size_t S, uint32_t K, double r_max, uint32_t* idx, double* dist,
+                        uint32_t* count) {
+    MSH_TRY(check_kbest_args(K, r_max, "msh_points_knearest"));
+    MSH_TRY(check_kbest_tree(t, kPoints, "msh_points_knearest"));
+    MSH_TRY(check_count(S, "msh_points_knearest"));
+    if (S == 0) return MSH_OK;
+    if (!q || !idx || !dist) { set_error("msh_points_knearest: null argument"); return MSH_EINVAL; }
+    HostCols c;  // count keeps its slab when the caller wants none (nothing is downloaded from it)
+    const auto cq = c.in(q, 3);
+    const auto cidx = c.out(idx, K);
+    const auto cdist = c.out(dist, K);
+    const auto ccnt = c.out(count, 1);
+    return host_call(t, S, c, kNoCut, [&](msh_tree* h, size_t n, const Slabs& d) {
+        return kbest_run(h, d[cq], n, K, r_max, KbOut{d[cidx], d[cdist], nullptr, nullptr, count ? d[ccnt] : nullptr},
+                         h->stream);
+    });
+}
+
+int msh_tree_knearest_device(msh_tree* t, const double* d_q, size_t S, uint32_t K, double r_max, uint32_t* d_face,
+                             double* d_dist, double* d_pt, uint32_t* d_part, uint32_t* d_count, void* stream) {
+    MSH_TRY(check_kbest_args(K, r_max, "msh_tree_knearest_device"));
+    MSH_TRY(check_kbest_tree(t, kTriangles, "msh_tree_knearest_device"));
+    MSH_TRY(check_count(S, "msh_tree_knearest_device"));
+    if (S == 0) return MSH_OK;
+    if (!d_q || !d_face || !d_dist) { set_error("msh_tree_knearest_device: null argument"); return MSH_EINVAL; }
+    return kbest_run(t, d_q, S, K, r_max, KbOut{d_face, d_dist, d_pt, d_part, d_count}, pick(t, stream));
+}
+
+int msh_tree_knearest(msh_tree* t, const double* q, size_t S, uint32_t K, double r_max, uint32_t* face, double* dist,
+                      double* pt, uint32_t* part, uint32_t* count) {
+    MSH_TRY(check_kbest_args(K, r_max, "msh_tree_knearest"));
+    MSH_TRY(check_kbest_tree(t, kTriangles, "msh_tree_knearest"));
+    MSH_TRY(check_count(S, "msh_tree_knearest"));
+    if (S == 0) return MSH_OK;
+    if (!q || !face || !dist) { set_error("msh_tree_knearest: null argument"); return MSH_EINVAL; }
+    HostCols c;  // only the columns the caller asked for take slab space: at K = 64 a row's points are 1.5 KB
+    const auto cq = c.in(q, 3);
+    const auto cface = c.out(face, K);
+    const auto cdist = c.out(dist, K);
+    const auto cpt = c.out(pt, pt ? 3 * (size_t)K : 0);
+    const auto cpart = c.out(part, part ? K : 0);
+    const auto ccnt = c.out(count, count ? 1 : 0);
+    return host_call(t, S, c, kNoCut, [&](msh_tree* h, size_t n, const Slabs& d) {
+        return kbest_run(h, d[cq], n, K, r_max,
+                         KbOut{d[cface], d[cdist], pt ? d[cpt] : nullptr, part ? d[cpart] : nullptr,
+                               count ? d[ccnt] : nullptr},
+                         h->stream);
+    });
+}
+
+int msh_tree_knearest_stats(msh_tree* t, const double* d_q, size_t S, uint32_t K, double r_max, uint64_t counts[4]) {
+    MSH_TRY(check_kbest_args(K, r_max, "msh_tree_knearest_stats"));
+    if (!t) { set_error("msh_tree_knearest_stats: null tree handle"); return MSH_EINVAL; }
+    MSH_TRY(check_kbest_tree(t, t->kind == kPoints ? kPoints : kTriangles, "msh_tree_knearest_stats"));
+    MSH_TRY(check_count(S, "msh_tree_knearest_stats"));
+    if (!counts) { set_error("msh_tree_knearest_stats: null argument"); return MSH_EINVAL; }
+    for (int k = 0; k < 4; ++k) counts[k] = 0;
+    if (S == 0) return MSH_OK;
+    if (!d_q) { set_error("msh_tree_knearest_stats: null argument"); return MSH_EINVAL; }
+    unsigned long long h[4] = {0, 0, 0, 0};
+    MSH_TRY(stats_call(t, d_q, nullptr, S, 4, h, 4, [&](const QueryOrder& ord, unsigned long long* d, hipStream_t s) {
+        return launch_kbest_stats(t, ord, S, K, r_max, d, s);
+    }));
+    for (int k = 0; k < 4; ++k) counts[k] = h[k];
+    return MSH_OK;
 }
 
 // ---- mesh geometry ----

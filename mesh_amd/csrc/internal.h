@@ -392,6 +392,27 @@ int launch_winding(msh_tree* tree, const void* table, const QueryOrder& ord, siz
 int launch_winding_stats(msh_tree* tree, const void* table, const QueryOrder& ord, size_t S, double beta,
                          unsigned long long* d_counts, hipStream_t s);
 
+// ---- K-nearest and radius-capped queries (kbest.hip) ----
+// Caller-order outputs of S rows of K ranks: id (S,K) vertex index or face id, dist (S,K); triangle trees also pt
+// (S,K,3) and part (S,K); count (S,).  pt, part and count may be nullptr.
+struct KbOut {
+    uint32_t* id;
+    double* dist;
+    double* pt;
+    uint32_t* part;
+    uint32_t* count;
+};
+// The first min(K, m) primitives within r_max of each row, ascending by (d2, id); unused ranks hold MSH_NO_FACE, +inf,
+// NaN and part 0.  Point trees and plain triangle trees, 1 <= K <= MSH_KNEAREST_MAX, r_max >= 0 (the caller checked).
+// ord: the rows' slot order (lazy: ord.q are the caller's rows).  d_inv: face -> leaf (face_leaf_map), needed for pt and
+// part.  Uses ws.res, ws.res_w, ws.flags and ws.spill.  Asynchronous on s.
+int launch_kbest(msh_tree* tree, const QueryOrder& ord, size_t S, uint32_t K, double r_max, const KbOut& o,
+                 const uint32_t* d_inv, hipStream_t s);
+// the same walk, untimed, no answers: d_counts[0] += nodes visited, [1] += primitives evaluated, [2] += list
+// insertions, [3] = max(the deepest stack any row reached)
+int launch_kbest_stats(msh_tree* tree, const QueryOrder& ord, size_t S, uint32_t K, double r_max,
+                       unsigned long long* d_counts, hipStream_t s);
+
 // ---- timing (devmem.cpp) ----
 struct TimedLaunch {
     const char* name;

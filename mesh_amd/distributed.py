@@ -304,6 +304,31 @@ def winding_number_device(tree, q, w, beta=None, stream=None):
         w.data_ptr(), _stream(q, stream)))
 
 
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def points_knearest_device(tree, q, k, idx, dist, count=None, max_distance=float("inf"), stream=None):
+    """Device-resident K nearest points (msh_points_knearest_device) on torch tensors: q (S,3) f64, idx (S,k) int32
+    viewed as uint32, dist (S,k) f64, count (S,) int32 or None; `tree` is a point tree handle.  Ranks past a row's count
+    hold 0xFFFFFFFF (-1 as int32) and inf.  Asynchronous on `stream` (default: torch's current stream)."""
+    k, r = _native.check_knearest(k, max_distance, "points_knearest_device")
+    _native.check(_native.lib().msh_points_knearest_device(
+        tree.ptr, q.data_ptr(), q.shape[0], k, r, idx.data_ptr(), dist.data_ptr(), _ptr(count), _stream(q, stream)))
+
+
+def tree_knearest_device(tree, q, k, face, dist, pt=None, part=None, count=None, max_distance=float("inf"),
+                         stream=None):
+    """Device-resident K nearest faces (msh_tree_knearest_device) on torch tensors: q (S,3) f64, face (S,k) int32
+    viewed as uint32, dist (S,k) f64, pt (S,k,3) f64, part (S,k) and count (S,) int32; pt, part and count may be None.
+    Asynchronous on `stream` (default: torch's current stream), except the handle's first call with pt or part, which
+    builds its face -> leaf map and waits for it."""
+    k, r = _native.check_knearest(k, max_distance, "tree_knearest_device")
+    _native.check(_native.lib().msh_tree_knearest_device(
+        tree.ptr, q.data_ptr(), q.shape[0], k, r, face.data_ptr(), dist.data_ptr(), _ptr(pt), _ptr(part), _ptr(count),
+        _stream(q, stream)))
+
+
 def sign_from_faces_device(tree, q, face, part, pt, sdist, stream=None):
     """The sign pass alone (msh_tree_sign_from_faces_device): sdist (S,) f64 for given (face, part, point) rows, e.g.
     the rows NarrowRing rebuilt with points_from_faces_device.  Asynchronous on `stream`."""

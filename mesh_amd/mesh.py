@@ -177,6 +177,18 @@ class Mesh(object):
     def closest_faces_and_points(self, vertices):
         return self._tree_for_batch(vertices).nearest(vertices)
 
+    def closest_vertices_k(self, vertices, k, max_distance=np.inf):
+        """(distances, indices) of the at most `k` vertices of this mesh within `max_distance` of every row of
+        `vertices`, nearest first, with scipy's KDTree.query conventions (search.ClosestPointTree.query on a tree built
+        for this call): a missing neighbour has index len(v) and distance inf."""
+        return search.ClosestPointTree(self).query(vertices, k, max_distance)
+
+    def closest_faces_and_points_k(self, vertices, k, max_distance=np.inf):
+        """(faces (S,k) uint32, points (S,k,3), distances (S,k)): the at most `k` faces within `max_distance` of every
+        row of `vertices`, nearest first (search.AabbTree.nearest_k on a tree built for this call; the walk does not
+        use the entry cut, so none is asked for)."""
+        return self.compute_aabb_tree().nearest_k(vertices, k, max_distance)
+
     def signed_distances(self, vertices):
         """Signed distance of every row of `vertices` to this mesh, (S,) float64: negative inside, positive outside
         (search.AabbTree.signed_distance on a tree built for this batch, as closest_faces_and_points builds one).

@@ -44,6 +44,18 @@ class AabbTree(object):
             return faces, parts, pts
         return faces, pts
 
+    def nearest_k(self, v_samples, k, max_distance=np.inf, nearest_part=False):
+        """The at most ``k`` faces within ``max_distance`` of each sample, nearest first: (faces (S,k) u32,
+        points (S,k,3) f64, distances (S,k) f64), with ``nearest_part=True`` (faces, parts (S,k) u32, points,
+        distances).  Ascending by (squared distance, face id), so ties go to the smaller face id, column 0 of an
+        uncapped answer is ``nearest``'s, and a smaller ``k`` gives a prefix.  Ranks past the faces in range (and
+        non-finite samples) hold face 0xFFFFFFFF, part 0, a NaN point and distance inf.  ``1 <= k <= 64``."""
+        from . import spatialsearch
+        faces, parts, pts, dist = spatialsearch.aabbtree_nearest_k(self.cpp_handle, _f64c(v_samples), k, max_distance)
+        if nearest_part:
+            return faces, parts, pts, dist
+        return faces, pts, dist
+
     def nearest_alongnormal(self, points, normals):
         """Nearest hit of the lines through ``points`` along +/-``normals``: (dist, face, point)."""
         from . import spatialsearch
@@ -159,6 +171,25 @@ class ClosestPointTree(object):
         idx, dist = N.empty_results(((S,), np.uint32), ((S,), np.float64))
         N.check(N.lib().msh_points_nearest(self._h.ptr, N.dptr(q), S, N.uptr(idx), N.dptr(dist)))
         return idx.astype(np.intp), dist
+
+    def query(self, v_samples, k=1, distance_upper_bound=np.inf):
+        """``scipy.spatial.KDTree.query(x, k, distance_upper_bound=...)`` on the GPU: (distances, indices) of the
+        ``k`` nearest vertices of each sample within the bound, nearest first, ties by vertex index.  Shapes as scipy's:
+        (S,) for ``k == 1``, else (S, k); a single (3,) point gives () / (k,).  Indices are ``np.intp``; a missing
+        neighbour has index ``n`` (the number of vertices) and distance inf.  ``1 <= k <= 64``."""
+        from . import spatialsearch
+        q = _f64c(v_samples)
+        single = q.ndim == 1
+        if single:
+            q = q.reshape(1, -1)
+        idx, dist, _ = spatialsearch.points_nearest_k(self._h, q, k, distance_upper_bound)
+        ind = idx.astype(np.intp)
+        ind[idx == N.NO_FACE] = np.asarray(self.v).shape[0]
+        if int(k) == 1:
+            dist, ind = dist[:, 0], ind[:, 0]
+        if single:
+            dist, ind = dist[0], ind[0]
+        return dist, ind
 
     def nearest(self, v_samples):
         # same container types as the reference's zip(*[...]) over per-sample KDTree queries

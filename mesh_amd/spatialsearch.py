@@ -11,7 +11,8 @@ constructions).  Deliberate differences:
     the method table, :35-40, and racy push_back, :393-402).
 Beyond the reference: ``aabbtree_intersections_pairs`` / ``aabbtree_selfintersections_pairs`` return which face
 hits which face, as a sorted (K, 2) pair list; ``aabbtree_signed_distance`` and ``aabbtree_winding_number`` answer
-inside / outside, the first on closed manifold meshes, the second on any triangle set.
+inside / outside, the first on closed manifold meshes, the second on any triangle set; ``aabbtree_nearest_k`` and
+``points_nearest_k`` return the K nearest faces or points of every row, optionally within a radius.
 """
 import numpy as np
 
@@ -117,6 +118,52 @@ def aabbtree_winding_number(tree, q, beta=None):
     w, = N.empty_results(((S,), np.float64))
     N.check(N.lib().msh_tree_winding_number(tree.ptr, N.dptr(q), S, beta, N.dptr(w)))
     return w
+
+
+def aabbtree_nearest_k(tree, q, k, max_distance=np.inf):
+    """(face (S,k) uint32, part (S,k) uint32, point (S,k,3) float64, dist (S,k) float64): for every row of ``q`` the
+    at most ``k`` faces within ``max_distance`` of it, nearest first (no reference counterpart).
+
+    The order is ascending by (squared distance, face id) with the exact squared distance ``aabbtree_nearest``
+    computes, so ties are decided by the face id, column 0 of an uncapped answer is ``aabbtree_nearest``'s, and a
+    smaller ``k`` gives a prefix of a larger one.  A row with fewer than ``k`` faces in range (or a non-finite row) is
+    padded with face 0xFFFFFFFF, part 0, a NaN point and distance inf.  ``1 <= k <= 64``; ``max_distance = 0`` keeps
+    exact hits only.  The extra faces of a tree built with them are included."""
+    tree = _tree(tree, "aabbtree_nearest_k")
+    if not isinstance(q, np.ndarray):
+        raise TypeError("aabbtree_nearest_k() argument 2 must be numpy.ndarray")
+    if q.ndim != 2 or q.shape[1] != 3:
+        raise ValueError("Input must be Nx3")
+    if tree.kind != "triangles":
+        raise TypeError("aabbtree_nearest_k: handle is not a triangle tree")
+    k, r = N.check_knearest(k, max_distance, "aabbtree_nearest_k")
+    q = np.ascontiguousarray(q, dtype=np.float64)
+    S = q.shape[0]
+    face, part, pt, dist = N.empty_results(((S, k), np.uint32), ((S, k), np.uint32), ((S, k, 3), np.float64),
+                                           ((S, k), np.float64))
+    N.check(N.lib().msh_tree_knearest(tree.ptr, N.dptr(q), S, k, r, N.uptr(face), N.dptr(dist), N.dptr(pt),
+                                      N.uptr(part), None))
+    return face, part, pt, dist
+
+
+def points_nearest_k(tree, q, k, max_distance=np.inf):
+    """(idx (S,k) uint32, dist (S,k) float64, count (S,) uint32): for every row of ``q`` the at most ``k`` points of a
+    point tree (``_native.build_points``) within ``max_distance`` of it, ascending by (squared distance, point index);
+    ranks past ``count`` hold 0xFFFFFFFF and inf.  ``search.ClosestPointTree.query`` is its scipy-shaped form."""
+    if not isinstance(tree, N.Handle) or tree.ptr is None:
+        raise TypeError("points_nearest_k: expected a point tree handle")
+    if not isinstance(q, np.ndarray):
+        raise TypeError("points_nearest_k() argument 2 must be numpy.ndarray")
+    if q.ndim != 2 or q.shape[1] != 3:
+        raise ValueError("Input must be Nx3")
+    if tree.kind != "points":
+        raise TypeError("points_nearest_k: handle is not a point tree")
+    k, r = N.check_knearest(k, max_distance, "points_nearest_k")
+    q = np.ascontiguousarray(q, dtype=np.float64)
+    S = q.shape[0]
+    idx, dist, count = N.empty_results(((S, k), np.uint32), ((S, k), np.float64), ((S,), np.uint32))
+    N.check(N.lib().msh_points_knearest(tree.ptr, N.dptr(q), S, k, r, N.uptr(idx), N.dptr(dist), N.uptr(count)))
+    return idx, dist, count
 
 
 def aabbtree_nearest_barycentric(tree, q):
