@@ -140,9 +140,8 @@ static int sort_batch_queries(msh_tree* t, const double* d_q, size_t n, size_t S
     const size_t meshes = n / S;  // of this launch
     if (meshes > 1) {
         MSH_TRY(mesh_keys(vals, n, S, keys, s));
-        int bits = 0;
-        while (bits < 32 && ((size_t)1 << bits) < meshes) ++bits;
-        MSH_TRY(radix_sort_pairs(keys, vals, ws.keys_alt.as<uint32_t>(), ws.vals_alt.as<uint32_t>(), n, bits, ws, s));
+        MSH_TRY(radix_sort_pairs(keys, vals, ws.keys_alt.as<uint32_t>(), ws.vals_alt.as<uint32_t>(), n, bits_for(meshes),
+                                 ws, s));
     }
     MSH_TRY(gather_rows(d_q, nullptr, vals, n, ws.qs.as<double>(), nullptr, ws.inv.as<uint32_t>(), s));
     *ord = QueryOrder{ws.qs.as<double>(), nullptr, vals, ws.inv.as<uint32_t>()};

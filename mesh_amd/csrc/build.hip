@@ -647,29 +647,27 @@ __global__ __launch_bounds__(kBlock) void k_pack_points(const double* __restrict
     out[k] = r;
 }
 
-static unsigned nblocks(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
 int tri_bounds(const double* d_v, const uint32_t* d_f, size_t T, double* d_lo, double* d_hi, hipStream_t s) {
-    k_tri_bounds<<<nblocks(T), kBlock, 0, s>>>(d_v, 0, d_f, T, T, d_lo, d_hi);
+    k_tri_bounds<<<blocks_for(T), kBlock, 0, s>>>(d_v, 0, d_f, T, T, d_lo, d_hi);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }
 
 int point_bounds(const double* d_v, size_t P, double* d_lo, double* d_hi, hipStream_t s) {
-    k_point_bounds<<<nblocks(3 * P), kBlock, 0, s>>>(d_v, P, d_lo, d_hi);
+    k_point_bounds<<<blocks_for(3 * P), kBlock, 0, s>>>(d_v, P, d_lo, d_hi);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }
 
 int pack_tri_leaves(const double* d_v, const uint32_t* d_f, const uint32_t* d_order, size_t T, uint32_t face_base,
                     TriRec* d_out, hipStream_t s) {
-    k_pack_tris<<<nblocks(T), kBlock, 0, s>>>(d_v, 0, d_f, d_order, T, T, face_base, d_out);
+    k_pack_tris<<<blocks_for(T), kBlock, 0, s>>>(d_v, 0, d_f, d_order, T, T, face_base, d_out);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }
 
 int pack_point_leaves(const double* d_v, const uint32_t* d_order, size_t P, PtRec* d_out, hipStream_t s) {
-    k_pack_points<<<nblocks(P), kBlock, 0, s>>>(d_v, d_order, P, d_out);
+    k_pack_points<<<blocks_for(P), kBlock, 0, s>>>(d_v, d_order, P, d_out);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }
@@ -685,7 +683,7 @@ static int build_obb_big(msh_tree* tree, bool triangles, const int4* ranges, int
         void* p = nullptr;
         ~Tmp() { if (p) (void)dfree(p); }
     } t_list, t_lr, t_cnt, t_items, t_off, t_frames, t_ext;
-    const unsigned nblk = (unsigned)(((size_t)nn + kBlock - 1) / kBlock);
+    const unsigned nblk = blocks_for((size_t)nn);
     MSH_HIP(dmalloc(&t_cnt.p, sizeof(unsigned)));
     MSH_HIP(hipMemsetAsync(t_cnt.p, 0, sizeof(unsigned), s));
     k_big_count<<<nblk, kBlock, 0, s>>>(ranges, nn, static_cast<unsigned*>(t_cnt.p));
@@ -737,7 +735,7 @@ static int build_obb_big(msh_tree* tree, bool triangles, const int4* ranges, int
     const int* d_off = static_cast<const int*>(t_off.p);
     ObbFrame* d_frames = static_cast<ObbFrame*>(t_frames.p);
     double* d_ext = static_cast<double*>(t_ext.p);
-    const unsigned nb = (nbig + kBlock - 1) / kBlock;
+    const unsigned nb = blocks_for(nbig);
     k_big_frame<<<nb, kBlock, 0, s>>>((int)nbig, d_lr, P, d_frames);
     if (triangles) {
         k_big_extent<true><<<(unsigned)ni, kBlock, 0, s>>>(tree->d_leaves, d_list, d_lr, d_items, d_frames, npm,
@@ -761,7 +759,7 @@ int build_obb(msh_tree* tree, bool triangles, bool defer) {
     hipStream_t s = tree->stream;
     const int4* ranges = tree->ws.ranges.as<int4>();
     const int npm = (int)(tree->T - 1);  // internal nodes per mesh
-    const unsigned lane_blocks = (unsigned)(((size_t)nn + kBlock - 1) / kBlock);
+    const unsigned lane_blocks = blocks_for((size_t)nn);
     // area prefix sums over all leaves (batched trees: the meshes' leaf ranges are disjoint)
     struct Tmp {
         void* p = nullptr;
@@ -775,7 +773,7 @@ int build_obb(msh_tree* tree, bool triangles, bool defer) {
     if (triangles) k_area_scan<true><<<(unsigned)nsb, kBlock, 0, s>>>(tree->d_leaves, nl, P, tot);
     else k_area_scan<false><<<(unsigned)nsb, kBlock, 0, s>>>(tree->d_leaves, nl, P, tot);
     k_area_scan_tops<<<1, kBlock, 0, s>>>(tot, nsb);
-    k_area_scan_add<<<(unsigned)(((size_t)nl + kBlock - 1) / kBlock), kBlock, 0, s>>>(P, nl, tot);
+    k_area_scan_add<<<blocks_for((size_t)nl), kBlock, 0, s>>>(P, nl, tot);
     MSH_HIP(hipGetLastError());
     int maxr = 0x7fffffff;
     if (triangles) {
@@ -816,7 +814,7 @@ int build_lbvh(msh_tree* tree, const double* d_lo, const double* d_hi, size_t T,
         return MSH_EINVAL;
     }
     // scene box
-    const unsigned rb = (unsigned)std::min<size_t>(1024, std::max<size_t>(1, (T + kBlock - 1) / kBlock));
+    const unsigned rb = (unsigned)std::min<size_t>(1024, std::max<size_t>(1, blocks_for(T)));
     MSH_TRY(ws.flags.reserve(std::max<size_t>((size_t)(rb + 1) * 6 * sizeof(double), T * sizeof(uint32_t) + 64)));
     double* part = ws.flags.as<double>();
     k_reduce_box<<<rb, kBlock, 0, s>>>(d_lo, d_hi, T, part);
@@ -853,7 +851,7 @@ int build_lbvh(msh_tree* tree, const double* d_lo, const double* d_hi, size_t T,
     MSH_TRY(ws.keys_alt.reserve(T * sizeof(uint32_t)));
     MSH_TRY(ws.vals_alt.reserve(T * sizeof(uint32_t)));
     uint32_t* keys = ws.keys.as<uint32_t>();
-    k_morton<<<nblocks(T), kBlock, 0, s>>>(d_lo, d_hi, T, T, d_box, keys, d_order);
+    k_morton<<<blocks_for(T), kBlock, 0, s>>>(d_lo, d_hi, T, T, d_box, keys, d_order);
     MSH_HIP(hipGetLastError());
     MSH_TRY(radix_sort_pairs(keys, d_order, ws.keys_alt.as<uint32_t>(), ws.vals_alt.as<uint32_t>(), T, 30, ws, s));
     tree->max_depth = 0;
@@ -869,7 +867,7 @@ int build_lbvh(msh_tree* tree, const double* d_lo, const double* d_hi, size_t T,
     uint32_t* flags = ws.flags.as<uint32_t>();
     unsigned* d_depth = flags + T;
     MSH_HIP(hipMemsetAsync(d_depth, 0, sizeof(unsigned), s));
-    k_karras<<<nblocks(T - 1), kBlock, 0, s>>>(keys, 1, (int)T, tree->d_nodes, parent, ws.ranges.as<int4>(), d_depth);
+    k_karras<<<blocks_for(T - 1), kBlock, 0, s>>>(keys, 1, (int)T, tree->d_nodes, parent, ws.ranges.as<int4>(), d_depth);
     MSH_HIP(hipGetLastError());
     unsigned depth = 0;
     MSH_HIP(hipMemcpyAsync(&depth, d_depth, sizeof(unsigned), hipMemcpyDeviceToHost, s));
@@ -882,22 +880,16 @@ int build_lbvh(msh_tree* tree, const double* d_lo, const double* d_hi, size_t T,
 // ---- batched build (C4: many meshes sharing one topology) ----
 int tri_bounds_batch(const double* d_v, size_t P, const uint32_t* d_f, size_t B, size_t T, double* d_lo, double* d_hi,
                      hipStream_t s) {
-    k_tri_bounds<<<nblocks(B * T), kBlock, 0, s>>>(d_v, P, d_f, B * T, T, d_lo, d_hi);
+    k_tri_bounds<<<blocks_for(B * T), kBlock, 0, s>>>(d_v, P, d_f, B * T, T, d_lo, d_hi);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }
 
 int pack_tri_leaves_batch(const double* d_v, size_t P, const uint32_t* d_f, const uint32_t* d_order, size_t B, size_t T,
                           TriRec* d_out, hipStream_t s) {
-    k_pack_tris<<<nblocks(B * T), kBlock, 0, s>>>(d_v, P, d_f, d_order, B * T, T, 0u, d_out);
+    k_pack_tris<<<blocks_for(B * T), kBlock, 0, s>>>(d_v, P, d_f, d_order, B * T, T, 0u, d_out);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
-}
-
-static int bits_for(size_t n) {  // bits needed for values in [0, n)
-    int b = 0;
-    while (b < 32 && ((size_t)1 << b) < n) ++b;
-    return b;
 }
 
 int build_lbvh_batch(msh_tree* tree, const double* d_lo, const double* d_hi, size_t T, uint32_t* d_order) {
@@ -917,15 +909,15 @@ int build_lbvh_batch(msh_tree* tree, const double* d_lo, const double* d_hi, siz
     MSH_TRY(ws.keys_alt.reserve(n * sizeof(uint32_t)));
     MSH_TRY(ws.vals_alt.reserve(n * sizeof(uint32_t)));
     uint32_t* keys = ws.keys.as<uint32_t>();
-    k_morton<<<nblocks(n), kBlock, 0, s>>>(d_lo, d_hi, n, T, tree->d_boxes, keys, d_order);
+    k_morton<<<blocks_for(n), kBlock, 0, s>>>(d_lo, d_hi, n, T, tree->d_boxes, keys, d_order);
     MSH_HIP(hipGetLastError());
     MSH_TRY(radix_sort_pairs(keys, d_order, ws.keys_alt.as<uint32_t>(), ws.vals_alt.as<uint32_t>(), n, 30, ws, s));
     if (B > 1) {
-        k_mesh_key<<<nblocks(n), kBlock, 0, s>>>(d_order, n, T, keys);
+        k_mesh_key<<<blocks_for(n), kBlock, 0, s>>>(d_order, n, T, keys);
         MSH_HIP(hipGetLastError());
         MSH_TRY(radix_sort_pairs(keys, d_order, ws.keys_alt.as<uint32_t>(), ws.vals_alt.as<uint32_t>(), n,
                                  bits_for(B), ws, s));
-        k_sorted_morton<<<nblocks(n), kBlock, 0, s>>>(d_lo, d_hi, d_order, n, T, tree->d_boxes, keys);
+        k_sorted_morton<<<blocks_for(n), kBlock, 0, s>>>(d_lo, d_hi, d_order, n, T, tree->d_boxes, keys);
         MSH_HIP(hipGetLastError());
     }
     const size_t nn = B * (T - 1);
@@ -936,7 +928,7 @@ int build_lbvh_batch(msh_tree* tree, const double* d_lo, const double* d_hi, siz
     uint32_t* flags = ws.flags.as<uint32_t>();
     unsigned* d_depth = flags + nn;
     MSH_HIP(hipMemsetAsync(d_depth, 0, sizeof(unsigned), s));
-    k_karras<<<nblocks(nn), kBlock, 0, s>>>(keys, (int)B, (int)T, tree->d_nodes, parent, ws.ranges.as<int4>(), d_depth);
+    k_karras<<<blocks_for(nn), kBlock, 0, s>>>(keys, (int)B, (int)T, tree->d_nodes, parent, ws.ranges.as<int4>(), d_depth);
     MSH_HIP(hipGetLastError());
     unsigned depth = 0;
     MSH_HIP(hipMemcpyAsync(&depth, d_depth, sizeof(unsigned), hipMemcpyDeviceToHost, s));
@@ -974,14 +966,14 @@ __global__ __launch_bounds__(kBlock) void k_query_morton_batch(const double* __r
 }
 
 int mesh_keys(const uint32_t* vals, size_t n, size_t per, uint32_t* keys, hipStream_t s) {
-    k_mesh_key<<<nblocks(n), kBlock, 0, s>>>(vals, n, per, keys);
+    k_mesh_key<<<blocks_for(n), kBlock, 0, s>>>(vals, n, per, keys);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }
 
 int query_morton_batch(const msh_tree* tree, const double* d_q, size_t n, size_t S, uint32_t* keys, uint32_t* vals,
                        hipStream_t s, size_t mesh0) {
-    k_query_morton_batch<<<nblocks(n), kBlock, 0, s>>>(d_q, n, S, tree->d_boxes + 6 * mesh0, keys, vals);
+    k_query_morton_batch<<<blocks_for(n), kBlock, 0, s>>>(d_q, n, S, tree->d_boxes + 6 * mesh0, keys, vals);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }

@@ -606,4 +606,40 @@ __device__ inline unsigned dequeue_tile(unsigned* counters, unsigned ntiles, uns
 
 __device__ inline bool finite3(const D3& q) { return isfinite(q.x) && isfinite(q.y) && isfinite(q.z); }
 
+// ---- shared by the one-lane-per-row walks over 64-slot tiles (winding.hip, kbest.hip) ----
+// Slot i of the launch's order: r = the caller's row (perm: slot -> row, nullptr: identity) and its point; a slot past
+// the end (!live) reads nothing and gets the origin.
+__device__ inline D3 load_slot_row(const double* __restrict__ q, const uint32_t* __restrict__ perm, size_t i, bool live,
+                                   size_t& r) {
+    r = live && perm ? (size_t)perm[i] : i;
+    return live ? D3{q[3 * r], q[3 * r + 1], q[3 * r + 2]} : D3{0.0, 0.0, 0.0};
+}
+__device__ inline unsigned long long wave_sum(unsigned long long x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    return x;
+}
+__device__ inline unsigned long long wave_max(unsigned long long x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long y = __shfl_xor(x, o);
+        x = y > x ? y : x;
+    }
+    return x;
+}
+// a wave's counters of an instrumented launch into stats[0..3]: three sums and a maximum (every lane calls it)
+__device__ inline void flush_stats4(unsigned long long* stats, unsigned long long s0, unsigned long long s1,
+                                    unsigned long long s2, unsigned long long mx) {
+    s0 = wave_sum(s0);
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    mx = wave_max(mx);
+    if ((threadIdx.x & 63) == 0) {
+        atomicAdd(&stats[0], s0);
+        atomicAdd(&stats[1], s1);
+        atomicAdd(&stats[2], s2);
+        atomicMax(&stats[3], mx);
+    }
+}
+
 }  // namespace msh

@@ -416,7 +416,7 @@ __global__ __launch_bounds__(kBlock) void k_points_from_faces(const TriRec* __re
 
 int face_leaf_map(const msh_tree* tree, uint32_t* d_inv, hipStream_t s) {
     const size_t T = tree->T;
-    k_face_leaf<<<(unsigned)((T + kBlock - 1) / kBlock), kBlock, 0, s>>>(static_cast<const TriRec*>(tree->d_leaves), T,
+    k_face_leaf<<<blocks_for(T), kBlock, 0, s>>>(static_cast<const TriRec*>(tree->d_leaves), T,
                                                                           d_inv);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
@@ -426,7 +426,7 @@ int points_from_faces(const msh_tree* tree, const uint32_t* d_inv, const double*
                       uint32_t* d_part, double* d_pt, hipStream_t s) {
     if (S == 0) return MSH_OK;
     TimedLaunch tl("points_from_faces", s);
-    k_points_from_faces<<<(unsigned)((S + kBlock - 1) / kBlock), kBlock, 0, s>>>(
+    k_points_from_faces<<<blocks_for(S), kBlock, 0, s>>>(
         static_cast<const TriRec*>(tree->d_leaves), d_inv, tree->T, d_q, S, d_face, d_part, d_pt);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
@@ -434,17 +434,17 @@ int points_from_faces(const msh_tree* tree, const uint32_t* d_inv, const double*
 
 int cut_hints(const msh_tree* tree, const uint32_t* d_face, size_t n, uint32_t* d_inv, int* d_hint, hipStream_t s) {
     const size_t T = tree->T;
-    k_face_leaf<<<(unsigned)((T + kBlock - 1) / kBlock), kBlock, 0, s>>>(static_cast<const TriRec*>(tree->d_leaves), T,
+    k_face_leaf<<<blocks_for(T), kBlock, 0, s>>>(static_cast<const TriRec*>(tree->d_leaves), T,
                                                                           d_inv);
     MSH_HIP(hipGetLastError());
-    k_cut_hint<<<(unsigned)((n + kBlock - 1) / kBlock), kBlock, 0, s>>>(d_face, n, T, d_inv, d_hint);
+    k_cut_hint<<<blocks_for(n), kBlock, 0, s>>>(d_face, n, T, d_inv, d_hint);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }
 
 int cut_centres(int G, const double* lo, const double* w, double* d_q, hipStream_t s) {
     const size_t n = (size_t)G * G * G;
-    k_cut_centres<<<(unsigned)((n + kBlock - 1) / kBlock), kBlock, 0, s>>>(G, lo[0], lo[1], lo[2], w[0], w[1], w[2], d_q);
+    k_cut_centres<<<blocks_for(n), kBlock, 0, s>>>(G, lo[0], lo[1], lo[2], w[0], w[1], w[2], d_q);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }
@@ -453,7 +453,7 @@ int cut_level(const msh_tree* tree, int G, const double* lo, const double* w, co
               uint32_t* d_rec, bool e4, hipStream_t s, const uint32_t* d_half, unsigned long long* d_nflag,
               int subdiv) {
     const size_t GB = ((size_t)G + 3) / 4;  // 4^3-cell bricks, one per wave
-    const unsigned nb = (unsigned)((GB * GB * GB * 64 + kBlock - 1) / kBlock);
+    const unsigned nb = blocks_for(GB * GB * GB * 64);
     const TriRec* tris = static_cast<const TriRec*>(tree->d_leaves);
     const double tm = tree_margin(tree->half_diag);
     TimedLaunch tl("cut_level", s);

@@ -386,6 +386,16 @@ int device_cus(int dev) {
     return cache[dev];
 }
 
+int plan_spill(Workspace& ws, int need, int lds_depth, unsigned nblk, uint2** spill, int* depth) {
+    *spill = nullptr;
+    *depth = 0;
+    if (need <= lds_depth) return MSH_OK;
+    *depth = need - lds_depth + 1;
+    MSH_TRY(ws.spill.reserve((size_t)nblk * kBlock * (size_t)*depth * sizeof(uint2)));
+    *spill = ws.spill.as<uint2>();
+    return MSH_OK;
+}
+
 // End of an asynchronous batched build: wait for its last kernel, free its temporaries, read its GPU time.  A kernel
 // failure of the build surfaces here (MSH_EDEVICE), at the first call that needs the tree.
 int finish_pending(msh_tree* t) {

@@ -75,8 +75,6 @@ __global__ __launch_bounds__(kBlock) void k_vertex_sum(const double* __restrict_
     vn[3 * i + 2] = z / nrm;
 }
 
-static unsigned nblk(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
 int vertex_normals(const double* d_v, size_t P, const uint32_t* d_f, size_t T, double* d_vn, Workspace& ws,
                    hipStream_t s, uint32_t* d_err) {
     if (P == 0) return MSH_OK;
@@ -97,18 +95,18 @@ int vertex_normals(const double* d_v, size_t P, const uint32_t* d_f, size_t T, d
     uint32_t* end = first + P;
     MSH_HIP(hipMemsetAsync(first, 0, 2 * P * sizeof(uint32_t), s));
     if (T) {
-        k_face_normals<<<nblk(T), kBlock, 0, s>>>(d_v, P, d_f, T, fn, d_err);
+        k_face_normals<<<blocks_for(T), kBlock, 0, s>>>(d_v, P, d_f, T, fn, d_err);
         MSH_HIP(hipGetLastError());
-        k_corner_keys<<<nblk(n), kBlock, 0, s>>>(d_f, n, P, ws.keys.as<uint32_t>(), ws.vals.as<uint32_t>());
+        k_corner_keys<<<blocks_for(n), kBlock, 0, s>>>(d_f, n, P, ws.keys.as<uint32_t>(), ws.vals.as<uint32_t>());
         MSH_HIP(hipGetLastError());
         int bits = 1;  // keys are <= P (P marks an out-of-range index)
         while (bits < 32 && ((size_t)1 << bits) <= P) ++bits;
         MSH_TRY(radix_sort_pairs(ws.keys.as<uint32_t>(), ws.vals.as<uint32_t>(), ws.keys_alt.as<uint32_t>(),
                                  ws.vals_alt.as<uint32_t>(), n, bits, ws, s));
-        k_vertex_ranges<<<nblk(n), kBlock, 0, s>>>(ws.keys.as<uint32_t>(), n, P, first, end);
+        k_vertex_ranges<<<blocks_for(n), kBlock, 0, s>>>(ws.keys.as<uint32_t>(), n, P, first, end);
         MSH_HIP(hipGetLastError());
     }
-    k_vertex_sum<<<nblk(P), kBlock, 0, s>>>(fn, ws.vals.as<uint32_t>(), first, end, P, d_vn);
+    k_vertex_sum<<<blocks_for(P), kBlock, 0, s>>>(fn, ws.vals.as<uint32_t>(), first, end, P, d_vn);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <chrono>
 #include <string>
 #include <vector>
@@ -431,6 +432,24 @@ extern thread_local std::vector<int> g_devices;  // devices of the trees built n
 int use_device(int dev);
 int current_device(int* dev);
 int device_cus(int dev);  // compute units of a device (cached; 256 when unknown): sizes the persistent grids
+// blocks of a grid with one thread per element
+inline unsigned blocks_for(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+// blocks of a persistent grid: the `wanted` ones, at most per_cu resident on each compute unit of the device
+inline unsigned persistent_blocks(int dev, size_t wanted, unsigned per_cu) {
+    return (unsigned)std::min<size_t>(wanted, (size_t)device_cus(dev) * per_cu);
+}
+// bits that hold the values 0 .. n - 1 (at most 32): the key width of a radix sort
+inline int bits_for(size_t n) {
+    int b = 0;
+    while (b < 32 && ((size_t)1 << b) < n) ++b;
+    return b;
+}
+// The spill area of a launch of nblk blocks whose lanes keep lds_depth stack entries in LDS (common.h stack_put) and
+// may hold `need`: nothing for need <= lds_depth, else ws.spill grown to *depth = need - lds_depth + 1 entries per lane
+// (block b's share starts at entry b * kBlock * *depth; a lane's entry sp >= lds_depth lies (sp - lds_depth) * kBlock
+// behind its first).  The one place that sizes it: a lane that pushes beyond lds_depth + *depth entries writes outside
+// the buffer.
+int plan_spill(Workspace& ws, int need, int lds_depth, unsigned nblk, uint2** spill, int* depth);
 // query workspaces handed from a freed triangle tree to the next one built on the device (devmem.cpp WsPool)
 void ws_pool_take(int dev, Workspace& ws);
 size_t ws_pool_trim();

@@ -142,20 +142,6 @@ struct KbPol {
     }
 };
 
-__device__ inline unsigned long long kb_wave_sum(unsigned long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
-}
-__device__ inline unsigned long long kb_wave_max(unsigned long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long y = __shfl_xor(x, o);
-        x = y > x ? y : x;
-    }
-    return x;
-}
-
 // E: the stack entries (Ent4 for trees of <= 2^20 leaves)
 template <bool TRI, int CAP, class E, bool STATS>
 __global__ __launch_bounds__(kBlock) void k_kbest(KbArgs a) {
@@ -174,8 +160,8 @@ __global__ __launch_bounds__(kBlock) void k_kbest(KbArgs a) {
     for (size_t tile = (size_t)blockIdx.x * (kBlock / 64) + (tid >> 6); tile < ntiles; tile += nwaves) {
         const size_t i = tile * 64 + lane;
         const bool live = i < a.S;
-        const size_t r = live && a.perm ? (size_t)a.perm[i] : i;  // the caller's row
-        const D3 q = live ? D3{a.q[3 * r], a.q[3 * r + 1], a.q[3 * r + 2]} : D3{0.0, 0.0, 0.0};
+        size_t r;  // the caller's row
+        const D3 q = load_slot_row(a.q, a.perm, i, live, r);
         const bool fin = live && finite3(q);
         double* const g_d2 = a.ld2 + tile * a.K * 64 + lane;  // this slot's entry 0 in the workspace
         uint32_t* const g_id = a.lid + tile * a.K * 64 + lane;
@@ -227,18 +213,7 @@ __global__ __launch_bounds__(kBlock) void k_kbest(KbArgs a) {
             n_nodes = n_leaves = 0;
         }
     }
-    if (STATS) {
-        t_nodes = kb_wave_sum(t_nodes);
-        t_leaves = kb_wave_sum(t_leaves);
-        t_ins = kb_wave_sum(t_ins);
-        deepest = kb_wave_max(deepest);
-        if (lane == 0) {
-            atomicAdd(&a.stats[0], t_nodes);
-            atomicAdd(&a.stats[1], t_leaves);
-            atomicAdd(&a.stats[2], t_ins);
-            atomicMax(&a.stats[3], deepest);
-        }
-    }
+    if (STATS) flush_stats4(a.stats, t_nodes, t_leaves, t_ins, deepest);
 }
 
 struct KbFinish {
@@ -335,15 +310,9 @@ static int launch_kb(msh_tree* tree, const QueryOrder& ord, size_t S, uint32_t K
     const size_t cap = K == 1 ? 0 : (K <= (uint32_t)kKbestLds ? kKbestLds : (K <= (uint32_t)kKbestLds2 ? kKbestLds2 : 0));
     const size_t lds = (size_t)kBlock * (kStack * (e4 ? sizeof(Ent4::T) : sizeof(Ent8::T)) + cap * 12);
     const unsigned per_cu = std::min<unsigned>(kKbestBlocksPerCU, (unsigned)(((size_t)160 << 10) / lds));
-    const unsigned nb = std::min<unsigned>((unsigned)((S + kBlock - 1) / kBlock),
-                                           (unsigned)device_cus(tree->device) * per_cu);
+    const unsigned nb = persistent_blocks(tree->device, blocks_for(S), per_cu);
     // the depth-first stack holds at most one entry per level of the path to the current node
-    const int need = tree->max_depth + 1;
-    if (need > kStack) {
-        a.spill_depth = need - kStack + 1;
-        MSH_TRY(ws.spill.reserve((size_t)nb * kBlock * (size_t)a.spill_depth * sizeof(uint2)));
-        a.spill = ws.spill.as<uint2>();
-    }
+    MSH_TRY(plan_spill(ws, tree->max_depth + 1, kStack, nb, &a.spill, &a.spill_depth));
     {
         TimedLaunch tl(STATS ? "kbest_stats" : "kbest", s);
         if (tri) {
@@ -372,9 +341,9 @@ static int launch_kb(msh_tree* tree, const QueryOrder& ord, size_t S, uint32_t K
     const size_t nthr = slots * K;
     TimedLaunch tl("kbest_finish", s);
     if (tri)
-        k_kbest_finish<true><<<(unsigned)((nthr + kBlock - 1) / kBlock), kBlock, 0, s>>>(f);
+        k_kbest_finish<true><<<blocks_for(nthr), kBlock, 0, s>>>(f);
     else
-        k_kbest_finish<false><<<(unsigned)((nthr + kBlock - 1) / kBlock), kBlock, 0, s>>>(f);
+        k_kbest_finish<false><<<blocks_for(nthr), kBlock, 0, s>>>(f);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }

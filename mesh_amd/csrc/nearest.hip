@@ -1027,13 +1027,7 @@ static int launch_knn(msh_tree* tree, KnnArgs a, hipStream_t s, const char* time
     // pass 2 lanes carry up to 2 kFront/64 dealt subtrees on top of a depth-first path
     const unsigned nblk2 = ncu * 2;  // pass 2: 2 blocks per CU
     const int need = tree->max_depth + 1 + 2 * kFront / 64 + 1 + (a.cut ? kCutK : 0);
-    a.spill = nullptr;
-    a.spill_depth = 0;
-    if (need > kStack) {
-        a.spill_depth = need - kStack + 1;
-        MSH_TRY(ws.spill.reserve((size_t)std::max(nblk_max, nblk2) * kBlock * (size_t)a.spill_depth * sizeof(uint2)));
-        a.spill = ws.spill.as<uint2>();
-    }
+    MSH_TRY(plan_spill(ws, need, kStack, std::max(nblk_max, nblk2), &a.spill, &a.spill_depth));
     a.budget = kBudget;
     bool list_pf = false;  // list path with the LDS node prefetch and 4-B stack entries (k_knn_list PF)
     {
@@ -1145,7 +1139,7 @@ static int launch_knn(msh_tree* tree, KnnArgs a, hipStream_t s, const char* time
             k_knn_coop<MODE, STATS><<<nblk2, kBlock, 0, s>>>(a);
             MSH_HIP(hipGetLastError());
             if (a.cand) {
-                k_knn_combine<MODE><<<(split_cap + kBlock - 1) / kBlock, kBlock, 0, s>>>(a);
+                k_knn_combine<MODE><<<blocks_for(split_cap), kBlock, 0, s>>>(a);
                 MSH_HIP(hipGetLastError());
             }
         }

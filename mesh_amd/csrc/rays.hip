@@ -567,19 +567,12 @@ static int launch_rays(msh_tree* tree, RayArgs a, size_t nrays, hipStream_t s, c
     for (int k = 0; k < 3; ++k) a.org[k] = tree->origin[k];
     a.M = tree->half_diag;
     a.ntiles = (unsigned)((nrays + 63) / 64);
-    const unsigned nblk = std::min<unsigned>((a.ntiles + 3) / 4, (unsigned)device_cus(tree->device) * 5u);
+    const unsigned nblk = persistent_blocks(tree->device, (a.ntiles + 3) / 4, 5);
     MSH_TRY(tree->ws.counters.reserve(9 * 32 * sizeof(unsigned)));
     a.counters = tree->ws.counters.as<unsigned>();
     MSH_HIP(hipMemsetAsync(a.counters, 0, 8 * 32 * sizeof(unsigned), s));
-    a.spill = nullptr;
-    a.spill_depth = 0;
-    const int lds_depth = MODE == 0 ? kAlongStack : kStack;
     const int need = tree->max_depth + 1 + (a.cut ? kCutK : 0);  // + the entry cut's start list
-    if (need > lds_depth) {
-        a.spill_depth = need - lds_depth + 1;
-        MSH_TRY(tree->ws.spill.reserve((size_t)nblk * kBlock * (size_t)a.spill_depth * sizeof(uint2)));
-        a.spill = tree->ws.spill.as<uint2>();
-    }
+    MSH_TRY(plan_spill(tree->ws, need, MODE == 0 ? kAlongStack : kStack, nblk, &a.spill, &a.spill_depth));
     TimedLaunch tl(timer, s);
     k_rays<MODE, STATS><<<nblk, kBlock, 0, s>>>(a);
     MSH_HIP(hipGetLastError());
@@ -658,7 +651,7 @@ static int vertex_order(msh_tree* t, size_t v0, size_t nv, const uint32_t** orde
     MSH_TRY(ws.vals_alt.reserve(nv * sizeof(uint32_t)));
     uint32_t* buf = nullptr;
     MSH_HIP(dmalloc(&buf, nv * sizeof(uint32_t)));
-    k_vertex_morton<<<(unsigned)((nv + kBlock - 1) / kBlock), kBlock, 0, s>>>(
+    k_vertex_morton<<<blocks_for(nv), kBlock, 0, s>>>(
         t->d_v, v0, nv, t->scene_lo[0], t->scene_lo[1], t->scene_lo[2], t->scene_hi[0], t->scene_hi[1],
         t->scene_hi[2], ws.keys.as<uint32_t>(), buf);
     int st = hipGetLastError() == hipSuccess ? MSH_OK : MSH_EDEVICE;

@@ -388,8 +388,6 @@ __global__ __launch_bounds__(kBlock) void k_rb_scatter(const uint32_t* __restric
     if (k) atomicAdd(&cnt[0], k);
 }
 
-static unsigned rb_blocks(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
 int resplit_tree(msh_tree* tree, const double* d_v, const uint32_t* d_f, size_t T, uint32_t* d_order, int log2K) {
     if (T < 3 || log2K <= 0) return MSH_OK;
     hipStream_t s = tree->stream;
@@ -427,13 +425,13 @@ int resplit_tree(msh_tree* tree, const double* d_v, const uint32_t* d_f, size_t 
     unsigned* cnt = static_cast<unsigned*>(t_cnt.p);  // [0] next level's segments, [1] the root's gap
     BNode* nodes2 = static_cast<BNode*>(t_nodes.p);
     int4* ranges2 = static_cast<int4*>(t_ranges.p);
-    const unsigned nb = rb_blocks(T);
+    const unsigned nb = blocks_for(T);
     const int4* ranges = ws.ranges.as<int4>();
 
     MSH_HIP(hipMemsetAsync(nodes2, 0, nn * sizeof(BNode), s));
     k_rb_prims<<<nb, kBlock, 0, s>>>(d_v, d_f, T, tree->origin[0], tree->origin[1], tree->origin[2], cen, area);
     k_rb_cut<<<nb, kBlock, 0, s>>>(tree->d_nodes, ranges, T, K, sbb[0], tabs[0].e, tabs[0].par);
-    k_rb_bignodes<<<rb_blocks(nn), kBlock, 0, s>>>(tree->d_nodes, ranges, nn, K, nodes2, ranges2, cnt + 1);
+    k_rb_bignodes<<<blocks_for(nn), kBlock, 0, s>>>(tree->d_nodes, ranges, nn, K, nodes2, ranges2, cnt + 1);
     MSH_HIP(hipGetLastError());
     int cur = 0, levels = 0;
     for (int level = 0;; ++level) {
@@ -443,7 +441,7 @@ int resplit_tree(msh_tree* tree, const double* d_v, const uint32_t* d_f, size_t 
         k_rb_frame<<<nb, kBlock, 0, s>>>(sbb[cur], tabs[cur].e, P, T, seg);
         k_rb_minmax<<<nb, kBlock, 0, s>>>(idx[cur], sbb[cur], cen, T, seg);
         k_rb_choose<<<nb, kBlock, 0, s>>>(sbb[cur], T, level, seg);
-        k_rb_flags<<<rb_blocks(T + 1), kBlock, 0, s>>>(idx[cur], sbb[cur], tabs[cur].e, cen, seg, T, flags);
+        k_rb_flags<<<blocks_for(T + 1), kBlock, 0, s>>>(idx[cur], sbb[cur], tabs[cur].e, cen, seg, T, flags);
         MSH_HIP(hipGetLastError());
         MSH_TRY(exclusive_scan_u32(flags, T + 1, ws, s));
         MSH_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned), s));

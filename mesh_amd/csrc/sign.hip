@@ -201,8 +201,6 @@ __global__ __launch_bounds__(kBlock) void k_sign_pass(const double* __restrict__
     sdist[i] = side < 0.0 ? -dist : dist;
 }
 
-static unsigned nblk(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
 static int bits_upto(size_t P) {  // keys are <= P (P marks an out-of-range index)
     int bits = 1;
     while (bits < 32 && ((size_t)1 << bits) <= P) ++bits;
@@ -232,24 +230,24 @@ int sign_table_build(const msh_tree* tree, const uint32_t* d_f, void* block, uin
     MSH_HIP(hipMemsetAsync(fn, 0, (T + P) * 3 * sizeof(double), s));  // fn and vpn are adjacent
     MSH_HIP(hipMemsetAsync(ang, 0, n * sizeof(double), s));
     MSH_HIP(hipMemcpyAsync(const_cast<uint32_t*>(tab.f), d_f, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    k_sign_faces<<<nblk(T), kBlock, 0, s>>>(static_cast<const TriRec*>(tree->d_leaves), tree->d_v, P, d_f, T, fn, ang,
+    k_sign_faces<<<blocks_for(T), kBlock, 0, s>>>(static_cast<const TriRec*>(tree->d_leaves), tree->d_v, P, d_f, T, fn, ang,
                                             d_counts);
     MSH_HIP(hipGetLastError());
     const int bits = bits_upto(P);
     // vertex pseudonormals
-    k_sign_corner_keys<<<nblk(n), kBlock, 0, s>>>(d_f, n, P, keys, vals);
+    k_sign_corner_keys<<<blocks_for(n), kBlock, 0, s>>>(d_f, n, P, keys, vals);
     MSH_HIP(hipGetLastError());
     MSH_TRY(radix_sort_pairs(keys, vals, ws.keys_alt.as<uint32_t>(), ws.vals_alt.as<uint32_t>(), n, bits, ws, s));
-    k_sign_vertex<<<nblk(n), kBlock, 0, s>>>(keys, vals, n, P, fn, ang, vpn);
+    k_sign_vertex<<<blocks_for(n), kBlock, 0, s>>>(keys, vals, n, P, fn, ang, vpn);
     MSH_HIP(hipGetLastError());
     // edge adjacency
-    k_sign_edge_max<<<nblk(n), kBlock, 0, s>>>(d_f, n, P, keys, vals);
+    k_sign_edge_max<<<blocks_for(n), kBlock, 0, s>>>(d_f, n, P, keys, vals);
     MSH_HIP(hipGetLastError());
     MSH_TRY(radix_sort_pairs(keys, vals, ws.keys_alt.as<uint32_t>(), ws.vals_alt.as<uint32_t>(), n, bits, ws, s));
-    k_sign_edge_min<<<nblk(n), kBlock, 0, s>>>(d_f, n, P, vals, keys);
+    k_sign_edge_min<<<blocks_for(n), kBlock, 0, s>>>(d_f, n, P, vals, keys);
     MSH_HIP(hipGetLastError());
     MSH_TRY(radix_sort_pairs(keys, vals, ws.keys_alt.as<uint32_t>(), ws.vals_alt.as<uint32_t>(), n, bits, ws, s));
-    k_sign_edge_runs<<<nblk(n), kBlock, 0, s>>>(d_f, n, vals, opp, d_counts);
+    k_sign_edge_runs<<<blocks_for(n), kBlock, 0, s>>>(d_f, n, vals, opp, d_counts);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }
@@ -258,7 +256,7 @@ int launch_sign_pass(const SignTable& tab, size_t T, size_t P, const double* d_q
                      const uint32_t* d_part, const double* d_pt, double* d_sdist, hipStream_t s) {
     if (S == 0) return MSH_OK;
     TimedLaunch tl("sign_pass", s);
-    k_sign_pass<<<nblk(S), kBlock, 0, s>>>(tab.fn, tab.vpn, tab.opp, tab.f, T, P, d_q, S, d_face, d_part, d_pt, d_sdist);
+    k_sign_pass<<<blocks_for(S), kBlock, 0, s>>>(tab.fn, tab.vpn, tab.opp, tab.f, T, P, d_q, S, d_face, d_part, d_pt, d_sdist);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }

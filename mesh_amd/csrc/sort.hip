@@ -584,7 +584,7 @@ int query_morton(const msh_tree* tree, const double* d_q, size_t S, uint32_t* ke
     // fit the box exactly cost 0.9 ms and gained nothing net)
     float lo[3], hi[3];
     query_box(tree, lo, hi);
-    k_query_morton<<<(unsigned)((S + kBlock - 1) / kBlock), kBlock, 0, s>>>(d_q, S, lo[0], lo[1], lo[2], hi[0], hi[1],
+    k_query_morton<<<blocks_for(S), kBlock, 0, s>>>(d_q, S, lo[0], lo[1], lo[2], hi[0], hi[1],
                                                                            hi[2], keys, vals);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
@@ -614,7 +614,7 @@ int gather_rows(const double* d_a, const double* d_b, const uint32_t* d_perm, si
                 uint32_t* d_inv, hipStream_t s) {
     if (S == 0) return MSH_OK;
     TimedLaunch tl("gather", s);
-    k_gather_rows<<<(unsigned)((S + kBlock - 1) / kBlock), kBlock, 0, s>>>(d_a, d_b, d_perm, S, d_as, d_bs, d_inv);
+    k_gather_rows<<<blocks_for(S), kBlock, 0, s>>>(d_a, d_b, d_perm, S, d_as, d_bs, d_inv);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }
@@ -644,7 +644,7 @@ int unpermute_results(const QRes* d_res, const double* d_w, int nw, const uint32
                       hipStream_t s) {
     if (S == 0) return MSH_OK;
     TimedLaunch tl("unpermute", s);
-    k_unpermute<<<(unsigned)((S + kBlock - 1) / kBlock), kBlock, 0, s>>>(d_res, d_w, nw, d_inv, S, o);
+    k_unpermute<<<blocks_for(S), kBlock, 0, s>>>(d_res, d_w, nw, d_inv, S, o);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }

@@ -4,7 +4,8 @@
 //   * aabbtree_n_selfintersects (aabb_normals.cpp:192-207, AABB_n_tree.h:107-116): one lane per mesh
 //     triangle, pairs sharing an exactly equal vertex coordinate are skipped.
 // K6b -- the same traversal without the early exit, for the pair lists (msh_tree_intersection_pairs,
-// msh_tree_self_intersection_pairs; no reference counterpart): k_tritri_all and its launchers at the end of the file.
+// msh_tree_self_intersection_pairs; no reference counterpart).  One kernel, k_tritri_all, walks for all of them: its
+// any-hit mode is K6, its count and fill modes are K6b.
 // The overlap test is the orientation-predicate test of Guigue & Devillers (2003) evaluated in fp64,
 // with a 2-D edge/containment test for the coplanar case.  Boxes: closed fp64 separating-axis test of
 // the triangle against each child's outward-rounded oriented box, on the node frame's three axes.
@@ -41,8 +42,11 @@ __device__ inline bool pt_in_tri_2d(double px, double py, const double* t) {
     return (d0 >= 0 && d1 >= 0 && d2 >= 0) || (d0 <= 0 && d1 <= 0 && d2 <= 0);
 }
 
-__device__ bool coplanar_tri_tri(const D3& p1, const D3& q1, const D3& r1, const D3& p2, const D3& q2, const D3& r2,
-                                 const D3& n) {
+// Not inlined: the walk calls it (through tri_tri_overlap, which follows it in the code object).  aligned(256): where
+// the two start relative to an instruction-cache line shows in a walk of coplanar triangles (300 coincident ones:
+// +0.2 % count, +0.6 % fill when three small kernels came to lie before them, at a function's default 4 B).
+__device__ __attribute__((aligned(256))) bool coplanar_tri_tri(const D3& p1, const D3& q1, const D3& r1, const D3& p2,
+                                                               const D3& q2, const D3& r2, const D3& n) {
     const double ax = fabs(n.x), ay = fabs(n.y), az = fabs(n.z);
     const int drop = (ax > az && ax >= ay) ? 0 : ((ay > az && ay > ax) ? 1 : 2);
     auto pr = [drop](const D3& p, double* o) {
@@ -150,111 +154,17 @@ __device__ inline bool obb_overlap(const TriProj& p, const float* ext) {
            (double)ext[1] <= p.hi[1] && p.lo[2] <= (double)ext[5] && (double)ext[2] <= p.hi[2];
 }
 
-struct TriArgs {
-    const BNode* nodes;
-    const TriRec* tris;
-    size_t T;
-    const TriRec* q;
-    size_t Tq;
-    int self_mode;
-    uint32_t* flags;
-    uint2* spill;
-    int spill_depth;
-    double org[3];  // tree origin
-};
-
-__global__ __launch_bounds__(kBlock) void k_tritri(TriArgs a) {
-    __shared__ uint2 stk[kStack * kBlock];
-    const int tid = threadIdx.x;
-    uint2* lds = stk + tid;
-    for (size_t i = (size_t)blockIdx.x * kBlock + tid; i < a.Tq; i += (size_t)gridDim.x * kBlock) {
-        uint2* spill = a.spill ? a.spill + (size_t)blockIdx.x * kBlock * (size_t)a.spill_depth + tid : nullptr;
-        D3 qa, qb, qc;
-        uint32_t qface;
-        load_tri(a.q, (int)i, qa, qb, qc, qface);
-        // query vertices relative to the tree origin (node bounds are origin-relative and padded >= 1 fp32
-        // ulp, far above the fp64 rounding of this subtraction)
-        const D3 org = D3{a.org[0], a.org[1], a.org[2]};
-        const D3 ra = vsub(qa, org), rb = vsub(qb, org), rc = vsub(qc, org);
-        bool hit = false;
-        auto leaf_test = [&](int leaf) {
-            D3 a0, a1, a2;
-            uint32_t f;
-            load_tri(a.tris, leaf, a0, a1, a2, f);
-            if (a.self_mode) {
-                if (veq(qa, a0) || veq(qa, a1) || veq(qa, a2) || veq(qb, a0) || veq(qb, a1) || veq(qb, a2) ||
-                    veq(qc, a0) || veq(qc, a1) || veq(qc, a2))
-                    return;
-            }
-            if (tri_tri_overlap(qa, qb, qc, a0, a1, a2)) hit = true;
-        };
-        if (a.T == 1) {
-            leaf_test(0);
-        } else {
-            int node = 0, sp = 0;
-            for (size_t guard = 0; guard < a.T; ++guard) {
-                const NodeV nd = load_node(a.nodes, node);
-                float e0[6], e1[6];
-                nd.extents(e0, e1);
-                const TriProj tp = tri_proj(frame_d(nd), ra, rb, rc);
-                bool h0 = obb_overlap(tp, e0);
-                bool h1 = obb_overlap(tp, e1);
-                const int c0 = nd.child(0), c1 = nd.child(1);
-                if (h0 && c0 < 0) { leaf_test(~c0); h0 = false; if (hit) break; }
-                if (h1 && c1 < 0) { leaf_test(~c1); h1 = false; if (hit) break; }
-                if (h0 && h1) {
-                    const uint2 e = make_uint2((unsigned)c1, 0u);
-                    stack_put(lds, spill, sp, e);
-                    ++sp;
-                    node = c0;
-                    continue;
-                }
-                if (h0) { node = c0; continue; }
-                if (h1) { node = c1; continue; }
-                if (sp == 0) break;
-                --sp;
-                node = (int)stack_get(lds, spill, sp).x;
-            }
-        }
-        a.flags[i] = hit ? 1u : 0u;
-    }
-}
-
-int launch_tri_intersect(const msh_tree* tree, const TriRec* d_qtris, size_t Tq, int self_mode, uint32_t* d_flags,
-                         hipStream_t s) {
-    if (Tq == 0) return MSH_OK;
-    TriArgs a{};
-    a.nodes = tree->d_nodes;
-    a.tris = static_cast<const TriRec*>(tree->d_leaves);
-    a.T = tree->T;
-    a.q = d_qtris;
-    a.Tq = Tq;
-    a.self_mode = self_mode;
-    for (int k = 0; k < 3; ++k) a.org[k] = tree->origin[k];
-    a.flags = d_flags;
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, tree->device) != hipSuccess || n <= 0) n = 256;
-    const unsigned nblk = (unsigned)std::min<size_t>((Tq + kBlock - 1) / kBlock, (size_t)n * 5);
-    msh_tree* t = const_cast<msh_tree*>(tree);
-    if (tree->max_depth + 1 > kStack) {
-        a.spill_depth = tree->max_depth + 1 - kStack + 1;
-        MSH_TRY(t->ws.spill.reserve((size_t)nblk * kBlock * (size_t)a.spill_depth * sizeof(uint2)));
-        a.spill = t->ws.spill.as<uint2>();
-    }
-    TimedLaunch tl("tritri", s);
-    k_tritri<<<nblk, kBlock, 0, s>>>(a);
-    MSH_HIP(hipGetLastError());
-    return MSH_OK;
-}
-
-// ---- all hits: the (query face, mesh face) pair list ----
-// Count, sum, scan, fill, order (DESIGN.md "Intersection pair lists").  k_tritri_all is k_tritri's traversal without
-// the early exit, run twice with the same body: kFill == false counts the hits of every row, kFill == true writes
-// them at the row's offset.  A row is the query triangle's index (query mode) or its face id (self mode: the queries
-// are the tree's own leaves, in leaf order; only leaves of a larger face id are kept, so every pair appears once, under
-// its smaller face, and the predicate gets the smaller face first).  Nothing but a row's own lane writes its count
-// or its segment, so the output does not depend on how lanes are scheduled.
+// ---- the walk: any hit, or all hits as the (query face, mesh face) pair list ----
+// Count, sum, scan, fill, order (DESIGN.md "Intersection pair lists").  k_tritri_all is one depth-first walk in three
+// modes.  kTriAny stops at a row's first hit and writes flags (a.counts[i] = 1 or 0, i the query triangle's index).
+// kTriCount and kTriFill walk to the end with the same body: the first counts the hits of every row, the second writes
+// them at the row's offset.  There a row is the query triangle's index (query mode) or its face id (self mode: the
+// queries are the tree's own leaves, in leaf order; only leaves of a larger face id are kept, so every pair appears
+// once, under its smaller face, and the predicate gets the smaller face first; the any-hit mode keeps every leaf, since
+// a face is flagged whatever the id order).  Nothing but a row's own lane writes its count or its segment, so the
+// output does not depend on how lanes are scheduled.
 constexpr int kLaneSort = 32;  // rows of up to this many hits are ordered by their own lane (k_tritri_all)
+enum { kTriAny = 0, kTriCount = 1, kTriFill = 2 };
 
 struct PairArgs {
     const BNode* nodes;
@@ -263,7 +173,7 @@ struct PairArgs {
     const TriRec* q;
     size_t Tq;
     int self_mode;
-    uint32_t* counts;         // per row; written by the count pass, read by the fill pass
+    uint32_t* counts;         // per row; written by the any-hit (flags) and the count pass, read by the fill pass
     const uint32_t* offsets;  // exclusive scan of counts (fill pass)
     uint32_t* ids;            // fill pass: mesh face of pair offsets[row] + k ...
     uint32_t* rows;           // ... and its row (nullptr when the lanes order their own rows)
@@ -274,9 +184,18 @@ struct PairArgs {
     double org[3];  // tree origin
 };
 
-// waves_per_eu(3): k_tritri's occupancy (162 VGPRs); without the hint the fill pass took 169, one over the step to 2 waves
-template <bool kFill>
+// self mode's filter: do the two triangles share an exactly equal vertex coordinate
+__device__ inline bool shares_vertex(const D3& qa, const D3& qb, const D3& qc, const D3& a0, const D3& a1, const D3& a2) {
+    return veq(qa, a0) || veq(qa, a1) || veq(qa, a2) || veq(qb, a0) || veq(qb, a1) || veq(qb, a2) || veq(qc, a0) ||
+           veq(qc, a1) || veq(qc, a2);
+}
+
+// waves_per_eu(3): the any-hit walk's occupancy (162 VGPRs); without the hint the fill pass took 169, one over the step
+// to 2 waves.  The modes differ by constexpr conditions inside the one body: the walk handed to the modes as a function
+// template over test / done lambdas compiled to 173 VGPRs (any hit) and 10 / 22 spilled ones (count / fill).
+template <int kMode>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) void k_tritri_all(PairArgs a) {
+    constexpr bool kAny = kMode == kTriAny, kFill = kMode == kTriFill;
     __shared__ uint2 stk[kStack * kBlock];
     const int tid = threadIdx.x;
     uint2* lds = stk + tid;
@@ -285,7 +204,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
         D3 qa, qb, qc;
         uint32_t qface;
         load_tri(a.q, (int)i, qa, qb, qc, qface);
-        const uint32_t row = a.self_mode ? qface : (uint32_t)i;
+        const uint32_t row = !kAny && a.self_mode ? qface : (uint32_t)i;
         // fill pass: this row's segment is [base, base + lim); a row without hits has nothing to walk for, and a walk
         // ends with its last hit (the count pass made the same walk to the end and found lim of them)
         uint32_t base = 0;
@@ -295,6 +214,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
             lim = a.counts[row];
             if (lim == 0) continue;
         }
+        // query vertices relative to the tree origin (node bounds are origin-relative and padded >= 1 fp32
+        // ulp, far above the fp64 rounding of this subtraction)
         const D3 org = D3{a.org[0], a.org[1], a.org[2]};
         const D3 ra = vsub(qa, org), rb = vsub(qb, org), rc = vsub(qc, org);
         uint32_t n = 0;
@@ -303,10 +224,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
             uint32_t f;
             load_tri(a.tris, leaf, a0, a1, a2, f);
             if (a.self_mode) {
-                if (f <= qface) return;
-                if (veq(qa, a0) || veq(qa, a1) || veq(qa, a2) || veq(qb, a0) || veq(qb, a1) || veq(qb, a2) ||
-                    veq(qc, a0) || veq(qc, a1) || veq(qc, a2))
-                    return;
+                if (!kAny && f <= qface) return;
+                if (shares_vertex(qa, qb, qc, a0, a1, a2)) return;
             }
             if (!tri_tri_overlap(qa, qb, qc, a0, a1, a2)) return;
             if (kFill && n < lim) {  // never at or beyond the segment's end, whatever the walk meets
@@ -327,8 +246,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
                 bool h0 = obb_overlap(tp, e0);
                 bool h1 = obb_overlap(tp, e1);
                 const int c0 = nd.child(0), c1 = nd.child(1);
-                if (h0 && c0 < 0) { leaf_test(~c0); h0 = false; }
-                if (h1 && c1 < 0) { leaf_test(~c1); h1 = false; }
+                if (h0 && c0 < 0) { leaf_test(~c0); h0 = false; if (kAny && n) break; }
+                if (h1 && c1 < 0) { leaf_test(~c1); h1 = false; if (kAny && n) break; }
                 if (kFill && n >= lim) break;
                 if (h0 && h1) {
                     const uint2 e = make_uint2((unsigned)c1, 0u);
@@ -344,7 +263,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
                 node = (int)stack_get(lds, spill, sp).x;
             }
         }
-        if (!kFill) a.counts[row] = n;
+        if (kAny) a.counts[i] = n ? 1u : 0u;
+        if (kMode == kTriCount) a.counts[row] = n;
         // Short rows are ordered by their own lane: the face ids of a row are distinct, so pair k of the row is the
         // smallest id above pair k - 1's -- lim^2 reads of the segment the lane has just written, lim <= kLaneSort.
         if (kFill && a.pairs) {
@@ -420,14 +340,12 @@ __global__ __launch_bounds__(kBlock) void k_pack_query_tris(const double* __rest
     if (!ok) atomicOr(err, 1ull);
 }
 
-static unsigned pair_blocks(const msh_tree* tree, size_t n) {
-    int cu = 0;
-    if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, tree->device) != hipSuccess || cu <= 0) cu = 256;
-    return (unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, (size_t)cu * 5);
-}
+// persistent grid: 5 blocks per CU at most, every lane strides over the rows
+static unsigned pair_blocks(const msh_tree* tree, size_t n) { return persistent_blocks(tree->device, blocks_for(n), 5); }
 
-// the traversal's arguments and, for a tree deeper than kStack, its spill area, sized as launch_tri_intersect does
-static int pair_args(msh_tree* t, const TriRec* d_qtris, size_t Tq, int self_mode, unsigned nblk, PairArgs* out) {
+// the walk's arguments (counts = d_counts) and, for a tree deeper than kStack, its spill area
+static int pair_args(msh_tree* t, const TriRec* d_qtris, size_t Tq, int self_mode, unsigned nblk, uint32_t* d_counts,
+                     PairArgs* out) {
     PairArgs a{};
     a.nodes = t->d_nodes;
     a.tris = static_cast<const TriRec*>(t->d_leaves);
@@ -436,13 +354,21 @@ static int pair_args(msh_tree* t, const TriRec* d_qtris, size_t Tq, int self_mod
     a.Tq = Tq;
     a.self_mode = self_mode;
     for (int k = 0; k < 3; ++k) a.org[k] = t->origin[k];
-    a.counts = t->ws.flags.as<uint32_t>();
-    if (t->max_depth + 1 > kStack) {
-        a.spill_depth = t->max_depth + 1 - kStack + 1;
-        MSH_TRY(t->ws.spill.reserve((size_t)nblk * kBlock * (size_t)a.spill_depth * sizeof(uint2)));
-        a.spill = t->ws.spill.as<uint2>();
-    }
+    a.counts = d_counts;
+    MSH_TRY(plan_spill(t->ws, t->max_depth + 1, kStack, nblk, &a.spill, &a.spill_depth));
     *out = a;
+    return MSH_OK;
+}
+
+int launch_tri_intersect(const msh_tree* tree, const TriRec* d_qtris, size_t Tq, int self_mode, uint32_t* d_flags,
+                         hipStream_t s) {
+    if (Tq == 0) return MSH_OK;
+    const unsigned nblk = pair_blocks(tree, Tq);
+    PairArgs a;
+    MSH_TRY(pair_args(const_cast<msh_tree*>(tree), d_qtris, Tq, self_mode, nblk, d_flags, &a));
+    TimedLaunch tl("tritri", s);
+    k_tritri_all<kTriAny><<<nblk, kBlock, 0, s>>>(a);
+    MSH_HIP(hipGetLastError());
     return MSH_OK;
 }
 
@@ -455,7 +381,7 @@ int pack_query_tris(msh_tree* tree, const double* d_qv, size_t Pq, const uint32_
     MSH_TRY(ws.q.reserve(Tq * sizeof(TriRec)));
     MSH_TRY(ws.counters.reserve(kPairWords * sizeof(unsigned long long)));
     MSH_HIP(hipMemsetAsync(ws.counters.ptr, 0, kPairWords * sizeof(unsigned long long), s));
-    k_pack_query_tris<<<(unsigned)((Tq + kBlock - 1) / kBlock), kBlock, 0, s>>>(
+    k_pack_query_tris<<<blocks_for(Tq), kBlock, 0, s>>>(
         d_qv, Pq, d_qf, Tq, ws.q.as<TriRec>(), ws.counters.as<unsigned long long>() + 2);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
@@ -471,10 +397,10 @@ int launch_tri_pairs_count(msh_tree* tree, const TriRec* d_qtris, size_t Tq, int
     if (!packed) MSH_HIP(hipMemsetAsync(d_tot, 0, kPairWords * sizeof(unsigned long long), s));
     const unsigned nblk = pair_blocks(tree, Tq);
     PairArgs a;
-    MSH_TRY(pair_args(tree, d_qtris, Tq, self_mode, nblk, &a));
+    MSH_TRY(pair_args(tree, d_qtris, Tq, self_mode, nblk, ws.flags.as<uint32_t>(), &a));
     {
         TimedLaunch tl("tritri_count", s);
-        k_tritri_all<false><<<nblk, kBlock, 0, s>>>(a);
+        k_tritri_all<kTriCount><<<nblk, kBlock, 0, s>>>(a);
         MSH_HIP(hipGetLastError());
     }
     {
@@ -506,7 +432,7 @@ int launch_tri_pairs_emit(msh_tree* tree, const TriRec* d_qtris, size_t Tq, int 
     }
     const unsigned nblk = pair_blocks(tree, Tq);
     PairArgs a;
-    MSH_TRY(pair_args(tree, d_qtris, Tq, self_mode, nblk, &a));
+    MSH_TRY(pair_args(tree, d_qtris, Tq, self_mode, nblk, ws.flags.as<uint32_t>(), &a));
     uint32_t* offsets = ws.ranges.as<uint32_t>();
     {
         TimedLaunch tl("tritri_scan", s);
@@ -520,26 +446,21 @@ int launch_tri_pairs_emit(msh_tree* tree, const TriRec* d_qtris, size_t Tq, int 
     a.n_emit = n_emit;
     {
         TimedLaunch tl("tritri_fill", s);
-        k_tritri_all<true><<<nblk, kBlock, 0, s>>>(a);
+        k_tritri_all<kTriFill><<<nblk, kBlock, 0, s>>>(a);
         MSH_HIP(hipGetLastError());
     }
     if (lane_order) return MSH_OK;
     // Long rows: the segments are in row order already; a stable sort of all K pairs by mesh face and then by row
     // leaves them sorted by (row, mesh face), in time linear in K however long a row is.
     TimedLaunch tl("tritri_order", s);
-    auto bits_of = [](size_t n) {  // bits that hold 0 .. n - 1
-        int b = 0;
-        while (n > 1 && ((size_t)1 << b) < n) ++b;
-        return b;
-    };
     uint32_t *ids = a.ids, *rows = a.rows, *ids_alt = ws.keys_alt.as<uint32_t>(), *rows_alt = ws.vals_alt.as<uint32_t>();
     bool alt = false;
-    MSH_TRY(radix_sort_pairs(ids, rows, ids_alt, rows_alt, K, bits_of(tree->T), ws, s, 0, &alt));
+    MSH_TRY(radix_sort_pairs(ids, rows, ids_alt, rows_alt, K, bits_for(tree->T), ws, s, 0, &alt));
     if (alt) { std::swap(ids, ids_alt); std::swap(rows, rows_alt); }
     alt = false;
-    MSH_TRY(radix_sort_pairs(rows, ids, rows_alt, ids_alt, K, bits_of(Tq), ws, s, 0, &alt));
+    MSH_TRY(radix_sort_pairs(rows, ids, rows_alt, ids_alt, K, bits_for(Tq), ws, s, 0, &alt));
     if (alt) { std::swap(ids, ids_alt); std::swap(rows, rows_alt); }
-    k_emit_pairs<<<(unsigned)((n_emit + kBlock - 1) / kBlock), kBlock, 0, s>>>(rows, ids, n_emit, d_pairs);
+    k_emit_pairs<<<blocks_for(n_emit), kBlock, 0, s>>>(rows, ids, n_emit, d_pairs);
     MSH_HIP(hipGetLastError());
     return MSH_OK;
 }

@@ -135,8 +135,6 @@ __global__ __launch_bounds__(kBlock) void k_wind_sweep(const BNode* __restrict__
     stamp[i] = k;
 }
 
-static unsigned nblk(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
 int winding_table_build(const msh_tree* tree, void* block, uint32_t* d_err, Workspace& ws, hipStream_t s) {
     const size_t T = tree->T;
     if (T < 2 || !tree->d_nodes || T > 0x7FFFFFFFull) {
@@ -155,8 +153,8 @@ int winding_table_build(const msh_tree* tree, void* block, uint32_t* d_err, Work
     // a node of height h is computed by launch h; the root's height is the deepest leaf's depth (<= max_depth)
     const int levels = std::max(tree->max_depth, 1);
     for (int k = 1; k <= levels; ++k) {
-        k_wind_sweep<<<nblk(n), kBlock, 0, s>>>(tree->d_nodes, static_cast<const TriRec*>(tree->d_leaves), T, org,
-                                                (uint32_t)k, sums, stamp, static_cast<WindRec*>(block), d_err);
+        k_wind_sweep<<<blocks_for(n), kBlock, 0, s>>>(tree->d_nodes, static_cast<const TriRec*>(tree->d_leaves), T, org,
+                                                      (uint32_t)k, sums, stamp, static_cast<WindRec*>(block), d_err);
         MSH_HIP(hipGetLastError());
     }
     // d_err[1] = the root's stamp (0: the sweeps did not reach it)
@@ -196,20 +194,6 @@ __device__ inline double wind_omega(const TriRec* __restrict__ tris, int leaf, c
     return 2.0 * atan2(num, den);
 }
 
-__device__ inline unsigned long long wave_sum(unsigned long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
-}
-__device__ inline unsigned long long wave_max(unsigned long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long y = __shfl_xor(x, o);
-        x = y > x ? y : x;
-    }
-    return x;
-}
-
 // The node step runs in fp32 -- the record is fp32 and the dipole's own error is ~1e-3 of its value --: the far test,
 // the dipole and v_rsq_f32 for |p - q|^-3; only the sum is fp64.  (In fp64, with a divide and a square root per
 // dipole, the walk ran 10 % slower on C3 and 16 % on C2 with the same errors to six digits)
@@ -227,9 +211,9 @@ __global__ __launch_bounds__(kBlock) void k_winding(WindArgs a) {
     for (size_t tile = (size_t)blockIdx.x * (kBlock / 64) + (tid >> 6); tile < ntiles; tile += nwaves) {
         const size_t i = tile * 64 + lane;
         const bool live = i < a.S;
-        const size_t r = live && a.perm ? (size_t)a.perm[i] : i;  // the caller's row
-        const D3 q = live ? D3{a.q[3 * r], a.q[3 * r + 1], a.q[3 * r + 2]} : D3{0.0, 0.0, 0.0};
-        const bool fin = live && isfinite(q.x) && isfinite(q.y) && isfinite(q.z);
+        size_t r;  // the caller's row
+        const D3 q = load_slot_row(a.q, a.perm, i, live, r);
+        const bool fin = live && finite3(q);
         const D3 qr = vsub(q, org);
         const float qx = (float)qr.x, qy = (float)qr.y, qz = (float)qr.z, beta = (float)a.beta;
         double acc = 0.0;  // solid angle, in visit order
@@ -286,18 +270,7 @@ __global__ __launch_bounds__(kBlock) void k_winding(WindArgs a) {
         }
         if (!STATS && live) a.w[r] = fin ? acc * 0.07957747154594767 : NAN;  // 1 / (4 pi)
     }
-    if (STATS) {
-        n_far = wave_sum(n_far);
-        n_open = wave_sum(n_open);
-        n_leaf = wave_sum(n_leaf);
-        deepest = wave_max(deepest);
-        if (lane == 0) {
-            atomicAdd(&a.stats[0], n_far);
-            atomicAdd(&a.stats[1], n_open);
-            atomicAdd(&a.stats[2], n_leaf);
-            atomicMax(&a.stats[3], deepest);
-        }
-    }
+    if (STATS) flush_stats4(a.stats, n_far, n_open, n_leaf, deepest);
 }
 
 template <bool STATS>
@@ -317,15 +290,9 @@ static int launch_wind(msh_tree* tree, const void* table, const QueryOrder& ord,
     a.stats = d_stats;
     for (int k = 0; k < 3; ++k) a.org[k] = tree->origin[k];
     // persistent grid: 8 blocks per CU at most (8 KB of LDS each), every wave strides over the tiles
-    const unsigned nb = std::min<unsigned>((unsigned)((S + kBlock - 1) / kBlock), (unsigned)device_cus(tree->device) * 8u);
-    const int need = tree->max_depth + 1;
-    a.cap = kWindStack;
-    if (need > kWindStack) {
-        a.spill_depth = need - kWindStack + 1;
-        MSH_TRY(tree->ws.spill.reserve((size_t)nb * kBlock * (size_t)a.spill_depth * sizeof(uint2)));
-        a.spill = tree->ws.spill.as<uint2>();
-        a.cap = kWindStack + a.spill_depth;
-    }
+    const unsigned nb = persistent_blocks(tree->device, blocks_for(S), 8);
+    MSH_TRY(plan_spill(tree->ws, tree->max_depth + 1, kWindStack, nb, &a.spill, &a.spill_depth));
+    a.cap = kWindStack + a.spill_depth;
     if (STATS) {
         k_winding<true><<<nb, kBlock, 0, s>>>(a);
     } else {

@@ -13,7 +13,8 @@ reloads, so a variant with loop spills is not worth a GPU session.
 
 --save FILE only writes the assembly; --diff FILE (the --save of another tree) compares the two kernel by kernel instead
 of reporting -- the .amdhsa_* block and the instruction text, comments dropped and labels renumbered -- and exits 1
-when any kernel differs.  Two compiles of one source differ only in the __hip_cuid_* symbol, so a refactor that should
+when any kernel differs (for such a kernel it also says whether the register, spill, LDS and private-segment figures of
+the metadata held).  Two compiles of one source differ only in the __hip_cuid_* symbol, so a refactor that should
 not touch the generated code shows "identical" for every kernel.  Both take --src FILE, a source of mesh_amd/csrc to
 compile (default nearest.hip; the report is of nearest.hip's kernels only), any number of times, or --src all for every
 .hip file: the kernels of all of them are compared by name, so code may move between files (knn.h's users, cutbuild.hip
@@ -106,20 +107,28 @@ def classify(ins):
 LEAN0 = "_ZN3msh10k_knn_leanILi0EEEvNS_7KnnArgsE"  # the headline's pass-1 kernel
 
 
-def report(s, name, tag):
-    """the record of the kernel with mangled name `name`, led by the caller's tag (which kernel it is)"""
-    meta = s[re.search(r"\.name:\s+" + name + r"\n", s).start():][:1500]
+def metadata(s, name):
+    """the register, spill, LDS and private-segment figures of the kernel with mangled name `name`, from the code
+    object's metadata"""
+    at = re.search(r"\.name:\s+" + name + r"\n", s).start()
     # the metadata lists a kernel's keys in alphabetical order around .name
-    head = s[:re.search(r"\.name:\s+" + name + r"\n", s).start()][-600:]
+    meta, head = s[at:][:1500], s[:at][-600:]
 
     def md(key, text):
         m = re.findall(r"\." + key + r":\s+(\d+)", text)
         return int(m[-1] if text is head else m[0]) if m else None
 
-    r = dict(tag)
+    r = {}
     for key in ("vgpr_count", "vgpr_spill_count", "sgpr_count", "sgpr_spill_count", "private_segment_fixed_size"):
         r[key] = md(key, meta)
     r["group_segment_fixed_size"] = md("group_segment_fixed_size", head)
+    return r
+
+
+def report(s, name, tag):
+    """the record of the kernel with mangled name `name`, led by the caller's tag (which kernel it is)"""
+    r = dict(tag)
+    r.update(metadata(s, name))
     # the names bench.py reads from profiles/pmc_traffic.json's isa record (waves_per_simd)
     r["vgpr"], r["vgpr_spill"], r["lds"] = r["vgpr_count"], r["vgpr_spill_count"], r["group_segment_fixed_size"]
     a = s.index(name + ":")
@@ -172,7 +181,12 @@ def kernels(s):
 def pre_split(name):
     """A pass-1 kernel of an assembly from before k_knn was split, under the name it has now: k_knn<MODE, STATS, LIST, PF,
     LEAN> (before k_knn_lean was a kernel of its own) and k_knn<MODE, STATS, LIST, PF> (before the list and the queue
-    path were)"""
+    path were); and the triangle walks from before k_tritri became a mode of k_tritri_all<kMode> (any hit 0, count 1,
+    fill 2; they were k_tritri and k_tritri_all<kFill>)"""
+    tri = {"_ZN3msh8k_tritriENS_7TriArgsE": 0, "_ZN3msh12k_tritri_allILb0EEEvNS_8PairArgsE": 1,
+           "_ZN3msh12k_tritri_allILb1EEEvNS_8PairArgsE": 2}
+    if name in tri:
+        return f"_ZN3msh12k_tritri_allILi{tri[name]}EEEvNS_8PairArgsE"
     m = re.fullmatch(r"_ZN3msh5k_knnILi(\d)ELb(\d)ELb(\d)ELb(\d)(?:ELb(\d))?EEEvNS_7KnnArgsE", name)
     if not m:
         return name
@@ -188,7 +202,9 @@ def diff(s, other):
     """Compare every kernel of this tree's assembly with the one saved by --save from another tree; 1 if any differs."""
     new = kernels(s)
     with open(other) as f:
-        old = {pre_split(k): v for k, v in kernels(f.read()).items()}
+        olds = f.read()
+    was = {pre_split(k): k for k in kernels(olds)}  # the name each kernel has in the other tree
+    old = {pre_split(k): v for k, v in kernels(olds).items()}
     bad = 0
     for name in sorted(set(old) | set(new)):
         if name not in old or name not in new:
@@ -199,6 +215,9 @@ def diff(s, other):
             a, b = old[name], new[name]
             k = next((j for j, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
             what = f"DIFFERS: {len(a)} -> {len(b)} lines, first at line {k}"
+            # a refactor may change a kernel's text but not what it occupies: say whether the metadata held
+            ma, mb = metadata(olds, was[name]), metadata(s, name)
+            what += "; metadata " + ("kept " + str(mb) if ma == mb else f"CHANGED {ma} -> {mb}")
         bad += what != "identical"
         print(f"{what:12s} {name}")
     print(f"{len(new)} kernels, {bad} not identical")

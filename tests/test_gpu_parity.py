@@ -767,6 +767,39 @@ def test_deep_tree_spill_path(oracle):
     assert np.array_equal(face[0], bf) and np.array_equal(pt, bpt)
 
 
+def test_deep_tree_rays(oracle):
+    # the ray walks on test_deep_tree_spill_path's mesh: both ray launches size a spill area for it (the alongnormal
+    # walk keeps a shallower LDS stack than the visibility walk)
+    rng = np.random.default_rng(22)
+    pts = np.vstack([rng.normal(size=(3000, 3)) * 1e-4, rng.normal(size=(3000, 3)) * 100])
+    v = np.repeat(pts, 3, axis=0) + rng.normal(size=(18000, 3)) * 1e-6
+    f = np.arange(18000, dtype=np.uint32).reshape(-1, 3)
+    from mesh_amd import spatialsearch, visibility
+    t = spatialsearch.aabbtree_compute(v, f)
+    assert t.info().max_depth > 16
+    # alongnormal: 384 lines through (or within 2e-4 of) the centroids of distinct faces, 128 far sources
+    rng = np.random.default_rng(61)
+    fi = rng.choice(6000, 384, replace=False)
+    n = rng.normal(size=(512, 3))
+    n /= np.linalg.norm(n, axis=1)[:, None]
+    p = np.vstack([v[f[fi].astype(np.int64)].mean(axis=1) + rng.uniform(-2e-4, 2e-4, (384, 1)) * n[:384],
+                   rng.normal(size=(128, 3)) * 50])
+    dist, face, pt = spatialsearch.aabbtree_nearest_alongnormal(t, p, n)
+    bd, bf, bpt = oracle.brute_alongnormal(v, f, p, n)
+    hs = bd < 1e100
+    print("alongnormal: %d hits, %d misses, %d hit faces in the cluster" % (hs.sum(), (~hs).sum(), (bf[hs] < 3000).sum()))
+    assert hs.sum() >= 300 and (~hs).sum() >= 100
+    assert np.array_equal(dist, bd) and np.array_equal(face, bf)
+    assert np.array_equal(pt[hs], bpt[hs])
+    # visibility: far, inside the cluster and between; the default min_dist of 1e-3 would step over the whole cluster
+    cams = np.array([[0, 0, 400], [1e-5, 2e-5, -1e-5], [0, 1e-3, 0], [-200, -200, -200]], dtype=np.float64)
+    vis, ndc = visibility.visibility_compute(cams=cams, tree=t, min_dist=1e-7)
+    bv, bn = oracle.brute_visibility(v, f, cams, min_dist=1e-7)
+    print("visibility: occluded per camera", (bv == 0).sum(axis=1))
+    assert all((row == 0).any() and (row == 1).any() for row in bv)
+    assert np.array_equal(vis, bv) and np.array_equal(ndc, bn)
+
+
 def test_build_deterministic_and_blob_roundtrip(oracle):
     import torch
     from mesh_amd import _native, spatialsearch
