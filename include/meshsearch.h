@@ -88,7 +88,8 @@ int msh_set_device(int device);
  * Mesh.closest_faces_and_points -> AabbTree.nearest, mesh.py:454-455 / search.py:26-30, has no device argument).
  * Trees built afterwards on the calling thread are built on the first device and replicated to the others
  * (blob pack + peer copy + unpack); the host-buffer entry points (msh_tree_nearest, _nearest_bary, _signed_distance,
- * _nearest_alongnormal, _knearest, msh_ntree_nearest, msh_points_nearest, msh_points_knearest: contiguous row ranges;
+ * _nearest_alongnormal, _knearest, _raycast, _occluded, msh_ntree_nearest, msh_points_nearest, msh_points_knearest:
+ * contiguous row ranges;
  * msh_visibility: camera ranges) then split their rows over the devices, one host thread and one chunk pipeline per device, so each
  * device's host link carries its share.  Calls below 32 MB of rows stay on the first device.  The answers equal
  * the one-device answers bit for bit (disjoint row ranges of the same arrays).  *_device entry points, batched
@@ -423,6 +424,52 @@ int msh_tree_knearest_device(msh_tree* tree, const double* d_q, size_t S, uint32
 /* untimed, same walk, point trees and plain triangle trees: counts[0] nodes visited, [1] primitives evaluated,
  * [2] list insertions, [3] deepest stack any row reached (entries).  d_q is a device pointer; synchronous. */
 int msh_tree_knearest_stats(msh_tree* tree, const double* d_q, size_t S, uint32_t K, double r_max, uint64_t counts[4]);
+
+/* ---- ray casting on plain triangle trees: first hit and occlusion for arbitrary rays ----
+ * Row i is an origin o, a direction d and a closed range [t0, t1] of the parameter t of the point o + t d.  d may have
+ * any non-zero length and is used as given (no (o + d) - o as for a CGAL Ray_3).  range is (S,2), or NULL for
+ * [0, +inf] on every row; t0 < 0 is taken as 0.
+ *   hit set    Leaf triangle j (face id j: the ids the pair lists use; on a tree of msh_tree_build_ex the main faces are
+ *              [0, T) and the extra faces [T, T + ET)) is a hit when the closed ray-triangle predicate that
+ *              nearest_alongnormal and visibility share reports a proper hit with t_j = num / den (num = n . (a - o),
+ *              den = n . d, n = (b - a) x (c - a)) and t0 <= t_j <= t1, or a coplanar overlap whose parameter interval,
+ *              clipped starting from [t0, t1] instead of [0, +inf], is not empty; then t_j is its lower end.
+ *   first hit  msh_tree_raycast: the lexicographic minimum of (t_j, j) over the hit set.  t (S,) f64, face (S,) u32,
+ *              and on request pt (S,3) and w (S,3) (either may be NULL): pt is nearest_alongnormal's construction,
+ *              CGAL's intersection(Plane_3(a, b, c), Line_3(o, o + d)) for a proper hit and o + t d for a coplanar hit
+ *              or where that construction's denominator is 0; w are the barycentric weights of pt that
+ *              msh_tree_nearest_bary computes, in the order of f[face].  A miss gives t = +inf, face = MSH_NO_FACE, pt
+ *              and w NaN.
+ *   occlusion  msh_tree_occluded: hit (S,) u8 is 1 iff the hit set is not empty; the walk stops at the first hit found.
+ * A row that cannot be cast -- a non-finite o or d, d = 0, a NaN in the range, t0 > t1 -- is answered as a miss; it is
+ * no error.  A row's answer is a function of (tree, o, d, range) alone: not of the other rows, their order, the
+ * chunking or the device split; no atomic decides an answer.
+ * Relations to the reference's ray queries (tests/test_gpu_raycast.py):
+ *   msh_tree_nearest_alongnormal(p, n) is the nearer, by (|pt - p|, face), of the first hits of (p, (p + n) - p) and
+ *   (p, (p - n) - p);
+ *   a vertex is visible to a camera iff (src, (src + dir) - src) is not occluded, src = v + min_dist dir and dir the unit
+ *   vector from v to the camera as msh_visibility forms them.
+ *   (One difference at the edge of fp64: a proper hit whose t_j = num / den is NaN -- a determinant overflowed -- is not
+ *   in the hit set here, since t0 <= NaN fails, while msh_visibility and nearest_alongnormal accept it.)
+ * Conditioning: the walk prunes by comparing fp32 box intervals of the geometric ray with the computed t; as for
+ * nearest_alongnormal, its margins cover constructions whose error stays below 2^-20 (|o| + M), M the scene's
+ * half-diagonal.
+ * Plain triangle trees only, with or without extra faces: normals-metric, point and batched trees and NULL handles are
+ * MSH_EINVAL, checked in the order handle, tree kind, row count, pointers.  S == 0 returns MSH_OK.  The walk starts at
+ * the root (the entry cut is neither built nor used), one lane per ray in the slot order of the origins.  The host
+ * entry points go through the pinned-slab pipeline and split their rows over the handle's replicas; the *_device ones
+ * take device pointers and are asynchronous on `stream`.  msh_timing_get names: "raycast", "occluded". */
+int msh_tree_raycast(msh_tree* tree, const double* o, const double* d, const double* range, size_t S, double* t,
+                     uint32_t* face, double* pt, double* w);
+int msh_tree_raycast_device(msh_tree* tree, const double* d_o, const double* d_d, const double* d_range, size_t S,
+                            double* d_t, uint32_t* d_face, double* d_pt, double* d_w, void* stream);
+int msh_tree_occluded(msh_tree* tree, const double* o, const double* d, const double* range, size_t S, uint8_t* hit);
+int msh_tree_occluded_device(msh_tree* tree, const double* d_o, const double* d_d, const double* d_range, size_t S,
+                             uint8_t* d_hit, void* stream);
+/* untimed, the same walks (any != 0: the occlusion walk), outputs not written: *nodes internal nodes loaded, *leaves
+ * leaf tests.  d_o, d_d, d_range are device pointers; synchronous. */
+int msh_tree_raycast_stats(msh_tree* tree, const double* d_o, const double* d_d, const double* d_range, size_t S,
+                           int any, uint64_t* nodes, uint64_t* leaves);
 
 /* ---- multi-GPU replication (RCCL broadcast of a built BVH over xGMI) ---- */
 /* Size of the flat device blob holding the mesh + BVH of a handle. */

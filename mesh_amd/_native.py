@@ -87,6 +87,12 @@ SIGNATURES = [
                                _c_double_p, _c_u32_p, _c_u32_p]),
     ("msh_tree_knearest_device", _i, [_vp, _vp, _sz, ctypes.c_uint32, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("msh_tree_knearest_stats", _i, [_vp, _vp, _sz, ctypes.c_uint32, ctypes.c_double, _c_u64_p]),
+    ("msh_tree_raycast", _i, [_vp, _c_double_p, _c_double_p, _c_double_p, _sz, _c_double_p, _c_u32_p, _c_double_p,
+                              _c_double_p]),
+    ("msh_tree_raycast_device", _i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    ("msh_tree_occluded", _i, [_vp, _c_double_p, _c_double_p, _c_double_p, _sz, ctypes.POINTER(ctypes.c_uint8)]),
+    ("msh_tree_occluded_device", _i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("msh_tree_raycast_stats", _i, [_vp, _vp, _vp, _vp, _sz, _i, _c_u64_p, _c_u64_p]),
     ("msh_tree_blob_size", _i, [_vp, ctypes.POINTER(_sz)]),
     ("msh_tree_blob_pack", _i, [_vp, _vp, _vp]),
     ("msh_tree_blob_unpack", _i, [_vp, _sz, _i, _vp, ctypes.POINTER(_vp)]),
@@ -366,6 +372,14 @@ class Handle(object):
         check(lib().msh_tree_knearest_stats(self.ptr, _vp(d_q), int(S), k, r, out))
         return tuple(int(x) for x in out)
 
+    def raycast_stats(self, d_o, d_d, S, d_range=None, any_hit=False):
+        """msh_tree_raycast_stats on S device rays at addresses d_o, d_d (and d_range, or None) -> (internal nodes
+        loaded, leaf tests) of the first-hit walks, or with any_hit of the occlusion walks; untimed, nothing written."""
+        nodes, leaves = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        check(lib().msh_tree_raycast_stats(self.ptr, _vp(d_o), _vp(d_d), _vp(d_range) if d_range else None, int(S),
+                                           1 if any_hit else 0, ctypes.byref(nodes), ctypes.byref(leaves)))
+        return nodes.value, leaves.value
+
     def free(self):
         if self.ptr:
             lib().msh_tree_free(self.ptr)
@@ -392,8 +406,8 @@ def source_build_id(extra=""):
     import os
     csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
     names = sorted(["sort.hip", "build.hip", "refine.hip", "nearest.hip", "cutbuild.hip", "rays.hip", "tritri.hip", "geometry.hip",
-                    "sign.hip", "winding.hip", "kbest.hip", "api.cpp", "devmem.cpp", "hostpipe.cpp", "entrycut.cpp", "blob.cpp",
-                    "hostpipe.h", "hostplan.h", "loaders.cpp", "common.h", "internal.h", "knn.h"])
+                    "sign.hip", "winding.hip", "kbest.hip", "raycast.hip", "api.cpp", "devmem.cpp", "hostpipe.cpp", "entrycut.cpp", "blob.cpp",
+                    "hostpipe.h", "hostplan.h", "loaders.cpp", "common.h", "internal.h", "knn.h", "rays.h"])
     h = hashlib.sha256()
     for p in [os.path.join(csrc, n) for n in names] + [os.path.join(csrc, "..", "..", "include", "meshsearch.h")]:
         with open(p, "rb") as fh:

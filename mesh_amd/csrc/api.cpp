@@ -165,6 +165,17 @@ static int check_tree(const msh_tree* t, int want_kind, const char* fn) {
     return use_device(t->device);
 }
 
+// point trees (want kPoints) or plain triangle trees (want kTriangles): the K-nearest and ray-casting entry points;
+// what: the query as the refusal of a normals-metric handle names it
+static int check_plain_tree(const msh_tree* t, int want, const char* fn, const char* what) {
+    MSH_TRY(check_tree(t, want, fn));
+    if (t->kind == kNormals) {
+        set_error("%s: normals-metric tree handle (%s a plain triangle tree)", fn, what);
+        return MSH_EINVAL;
+    }
+    return MSH_OK;
+}
+
 static int check_batch(const msh_tree* t, const char* fn) {
     if (!t) {
         set_error("%s: null tree handle", fn);
@@ -975,6 +986,88 @@ int msh_tree_nearest_alongnormal(msh_tree* t, const double* p, const double* n, 
     });
 }
 
+// ---- ray casting: first hit and occlusion for arbitrary rays (raycast.hip) ----
+
+// one launch over the rays in the slot order of their origins, from the root (no entry cut)
+static int raycast_run(msh_tree* t, const double* d_o, const double* d_d, const double* d_range, size_t S,
+                       const RayOut& o, hipStream_t s) {
+    WsOrder order(t, s);
+    QueryOrder ord;
+    MSH_TRY(sort_queries(t, d_o, d_d, S, s, &ord, true));
+    return launch_raycast(t, ord, d_range, S, o, nullptr, s);
+}
+
+int msh_tree_raycast_device(msh_tree* t, const double* d_o, const double* d_d, const double* d_range, size_t S,
+                            double* d_t, uint32_t* d_face, double* d_pt, double* d_w, void* stream) {
+    MSH_TRY(check_plain_tree(t, kTriangles, "msh_tree_raycast_device", "ray casting needs"));
+    MSH_TRY(check_count(S, "msh_tree_raycast_device"));
+    if (S == 0) return MSH_OK;
+    if (!d_o || !d_d || !d_t || !d_face) { set_error("msh_tree_raycast_device: null argument"); return MSH_EINVAL; }
+    return raycast_run(t, d_o, d_d, d_range, S, RayOut{false, d_t, d_face, d_pt, d_w, nullptr}, pick(t, stream));
+}
+
+int msh_tree_raycast(msh_tree* t, const double* o, const double* d, const double* range, size_t S, double* tt,
+                     uint32_t* face, double* pt, double* w) {
+    MSH_TRY(check_plain_tree(t, kTriangles, "msh_tree_raycast", "ray casting needs"));
+    MSH_TRY(check_count(S, "msh_tree_raycast"));
+    if (S == 0) return MSH_OK;
+    if (!o || !d || !tt || !face) { set_error("msh_tree_raycast: null argument"); return MSH_EINVAL; }
+    HostCols c;  // a NULL range and the outputs the caller did not ask for take no slab space
+    const auto co = c.in(o, 3), cd = c.in(d, 3);
+    const auto cr = c.in(range, range ? 2 : 0);
+    const auto ct = c.out(tt, 1);
+    const auto cpt = c.out(pt, pt ? 3 : 0);
+    const auto cw = c.out(w, w ? 3 : 0);
+    const auto cface = c.out(face, 1);  // the 4-B column last: the fp64 columns stay 8-B aligned in a slab of odd rows
+    return host_call(t, S, c, kNoCut, [&](msh_tree* h, size_t n, const Slabs& s) {
+        return raycast_run(h, s[co], s[cd], range ? s[cr] : nullptr, n,
+                           RayOut{false, s[ct], s[cface], pt ? s[cpt] : nullptr, w ? s[cw] : nullptr, nullptr},
+                           h->stream);
+    });
+}
+
+int msh_tree_occluded_device(msh_tree* t, const double* d_o, const double* d_d, const double* d_range, size_t S,
+                             uint8_t* d_hit, void* stream) {
+    MSH_TRY(check_plain_tree(t, kTriangles, "msh_tree_occluded_device", "ray casting needs"));
+    MSH_TRY(check_count(S, "msh_tree_occluded_device"));
+    if (S == 0) return MSH_OK;
+    if (!d_o || !d_d || !d_hit) { set_error("msh_tree_occluded_device: null argument"); return MSH_EINVAL; }
+    return raycast_run(t, d_o, d_d, d_range, S, RayOut{true, nullptr, nullptr, nullptr, nullptr, d_hit},
+                       pick(t, stream));
+}
+
+int msh_tree_occluded(msh_tree* t, const double* o, const double* d, const double* range, size_t S, uint8_t* hit) {
+    MSH_TRY(check_plain_tree(t, kTriangles, "msh_tree_occluded", "ray casting needs"));
+    MSH_TRY(check_count(S, "msh_tree_occluded"));
+    if (S == 0) return MSH_OK;
+    if (!o || !d || !hit) { set_error("msh_tree_occluded: null argument"); return MSH_EINVAL; }
+    HostCols c;
+    const auto co = c.in(o, 3), cd = c.in(d, 3);
+    const auto cr = c.in(range, range ? 2 : 0);
+    const auto chit = c.out(hit, 1);
+    return host_call(t, S, c, kNoCut, [&](msh_tree* h, size_t n, const Slabs& s) {
+        return raycast_run(h, s[co], s[cd], range ? s[cr] : nullptr, n,
+                           RayOut{true, nullptr, nullptr, nullptr, nullptr, s[chit]}, h->stream);
+    });
+}
+
+int msh_tree_raycast_stats(msh_tree* t, const double* d_o, const double* d_d, const double* d_range, size_t S, int any,
+                           uint64_t* nodes, uint64_t* leaves) {
+    MSH_TRY(check_plain_tree(t, kTriangles, "msh_tree_raycast_stats", "ray casting needs"));
+    MSH_TRY(check_count(S, "msh_tree_raycast_stats"));
+    if (!nodes || !leaves) { set_error("msh_tree_raycast_stats: null argument"); return MSH_EINVAL; }
+    *nodes = *leaves = 0;
+    if (S == 0) return MSH_OK;
+    if (!d_o || !d_d) { set_error("msh_tree_raycast_stats: null argument"); return MSH_EINVAL; }
+    unsigned long long h[2] = {0, 0};
+    MSH_TRY(stats_call(t, d_o, d_d, S, 2, h, 2, [&](const QueryOrder& ord, unsigned long long* d, hipStream_t s) {
+        return launch_raycast(t, ord, d_range, S, RayOut{any != 0, nullptr, nullptr, nullptr, nullptr, nullptr}, d, s);
+    }));
+    *nodes = h[0];
+    *leaves = h[1];
+    return MSH_OK;
+}
+
 static void host_tris(const double* v, const uint32_t* f, size_t T, std::vector<TriRec>& out) {
     out.resize(T);
     for (size_t t = 0; t < T; ++t) {
@@ -1237,6 +1330,7 @@ int msh_points_nearest(msh_tree* t, const double* q, size_t S, uint32_t* idx, do
 }
 
 // ---- K-nearest and radius-capped queries (kbest.hip) ----
+static const char* const kKbestNeeds = "K-nearest queries need";
 static int check_kbest_args(uint32_t K, double r_max, const char* fn) {
     if (K < 1 || K > MSH_KNEAREST_MAX) {
         set_error("%s: K must be in 1..%d, got %u", fn, MSH_KNEAREST_MAX, K);
@@ -1244,16 +1338,6 @@ static int check_kbest_args(uint32_t K, double r_max, const char* fn) {
     }
     if (!(r_max >= 0.0)) {
         set_error("%s: r_max must be >= 0 (+inf: no cap), got %g", fn, r_max);
-        return MSH_EINVAL;
-    }
-    return MSH_OK;
-}
-
-// point trees (want kPoints) or plain triangle trees (want kTriangles)
-static int check_kbest_tree(const msh_tree* t, int want, const char* fn) {
-    MSH_TRY(check_tree(t, want, fn));
-    if (t->kind == kNormals) {
-        set_error("%s: normals-metric tree handle (K-nearest queries need a plain triangle tree)", fn);
         return MSH_EINVAL;
     }
     return MSH_OK;
@@ -1272,7 +1356,7 @@ static int kbest_run(msh_tree* t, const double* d_q, size_t S, uint32_t K, doubl
 int msh_points_knearest_device(msh_tree* t, const double* d_q, size_t S, uint32_t K, double r_max, uint32_t* d_idx,
                                double* d_dist, uint32_t* d_count, void* stream) {
     MSH_TRY(check_kbest_args(K, r_max, "msh_points_knearest_device"));  // before the handle, as winding's beta
-    MSH_TRY(check_kbest_tree(t, kPoints, "msh_points_knearest_device"));
+    MSH_TRY(check_plain_tree(t, kPoints, "msh_points_knearest_device", kKbestNeeds));
     MSH_TRY(check_count(S, "msh_points_knearest_device"));
     if (S == 0) return MSH_OK;
     if (!d_q || !d_idx || !d_dist) { set_error("msh_points_knearest_device: null argument"); return MSH_EINVAL; }
@@ -1282,7 +1366,7 @@ int msh_points_knearest_device(msh_tree* t, const double* d_q, size_t S, uint32_
 int msh_points_knearest(msh_tree* t, const double* q, size_t S, uint32_t K, double r_max, uint32_t* idx, double* dist,
                         uint32_t* count) {
     MSH_TRY(check_kbest_args(K, r_max, "msh_points_knearest"));
-    MSH_TRY(check_kbest_tree(t, kPoints, "msh_points_knearest"));
+    MSH_TRY(check_plain_tree(t, kPoints, "msh_points_knearest", kKbestNeeds));
     MSH_TRY(check_count(S, "msh_points_knearest"));
     if (S == 0) return MSH_OK;
     if (!q || !idx || !dist) { set_error("msh_points_knearest: null argument"); return MSH_EINVAL; }
@@ -1300,7 +1384,7 @@ int msh_points_knearest(msh_tree* t, const double* q, size_t S, uint32_t K, doub
 int msh_tree_knearest_device(msh_tree* t, const double* d_q, size_t S, uint32_t K, double r_max, uint32_t* d_face,
                              double* d_dist, double* d_pt, uint32_t* d_part, uint32_t* d_count, void* stream) {
     MSH_TRY(check_kbest_args(K, r_max, "msh_tree_knearest_device"));
-    MSH_TRY(check_kbest_tree(t, kTriangles, "msh_tree_knearest_device"));
+    MSH_TRY(check_plain_tree(t, kTriangles, "msh_tree_knearest_device", kKbestNeeds));
     MSH_TRY(check_count(S, "msh_tree_knearest_device"));
     if (S == 0) return MSH_OK;
     if (!d_q || !d_face || !d_dist) { set_error("msh_tree_knearest_device: null argument"); return MSH_EINVAL; }
@@ -1310,7 +1394,7 @@ int msh_tree_knearest_device(msh_tree* t, const double* d_q, size_t S, uint32_t 
 int msh_tree_knearest(msh_tree* t, const double* q, size_t S, uint32_t K, double r_max, uint32_t* face, double* dist,
                       double* pt, uint32_t* part, uint32_t* count) {
     MSH_TRY(check_kbest_args(K, r_max, "msh_tree_knearest"));
-    MSH_TRY(check_kbest_tree(t, kTriangles, "msh_tree_knearest"));
+    MSH_TRY(check_plain_tree(t, kTriangles, "msh_tree_knearest", kKbestNeeds));
     MSH_TRY(check_count(S, "msh_tree_knearest"));
     if (S == 0) return MSH_OK;
     if (!q || !face || !dist) { set_error("msh_tree_knearest: null argument"); return MSH_EINVAL; }
@@ -1332,7 +1416,7 @@ int msh_tree_knearest(msh_tree* t, const double* q, size_t S, uint32_t K, double
 int msh_tree_knearest_stats(msh_tree* t, const double* d_q, size_t S, uint32_t K, double r_max, uint64_t counts[4]) {
     MSH_TRY(check_kbest_args(K, r_max, "msh_tree_knearest_stats"));
     if (!t) { set_error("msh_tree_knearest_stats: null tree handle"); return MSH_EINVAL; }
-    MSH_TRY(check_kbest_tree(t, t->kind == kPoints ? kPoints : kTriangles, "msh_tree_knearest_stats"));
+    MSH_TRY(check_plain_tree(t, t->kind == kPoints ? kPoints : kTriangles, "msh_tree_knearest_stats", kKbestNeeds));
     MSH_TRY(check_count(S, "msh_tree_knearest_stats"));
     if (!counts) { set_error("msh_tree_knearest_stats: null argument"); return MSH_EINVAL; }
     for (int k = 0; k < 4; ++k) counts[k] = 0;

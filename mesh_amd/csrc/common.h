@@ -105,6 +105,9 @@ __host__ __device__ inline float f32_up(double x) {
     return (double)f < x ? nextafterf(f, INFINITY) : f;
 }
 
+// fp32 rounding of x towards -inf
+__host__ __device__ inline float f32_down(double x) { return -f32_up(-x); }
+
 // node writers shared by the build and the host property test: frame pairs (n_k, t_k) and scale words
 __host__ __device__ inline void encode_frame(float* f, const float* n, const float* t) {
     f[0] = n[0]; f[1] = t[0]; f[2] = n[1]; f[3] = t[1]; f[4] = n[2]; f[5] = t[2];
@@ -516,6 +519,46 @@ __host__ __device__ inline void ray_child_line_dist2(const NodeV& nd, const RayF
 #endif
     k0 = g0 * g0 * (1.f - 2.f * w);
     k1 = g1 * g1 * (1.f - 2.f * w);
+}
+
+// Rays with a parameter range (raycast.hip): the model of o + t d for t in [t0, t1], 0 <= t0 <= t1 (not NaN), d used as
+// given.  With L = |d| the model's parameter is s = t L, and the range clips the model interval outward only: slo =
+// max(0, t0 L rounded down), shi = min(scene bound, t1 L rounded up), the fp64 products first moved outward by 2^-40
+// against their own roundings; a non-finite product keeps the scene bound.  The fp64 leaf test decides the exact range.
+// A direction whose squared length leaves fp64's normal range (no accurate L) takes every box.  *len = L.
+__host__ __device__ inline RayF make_rayf_range(const D3& o, const D3& d, double M, double t0, double t1, double* len) {
+    RayF r = make_rayf(o, d, M, false);
+    const double dd = vdot(d, d), L = sqrt(dd);
+    *len = L;
+    if (!(dd > 1e-270)) r.wide = true;
+    if (r.wide) return r;
+    const double lo = t0 * L / kSlack, hi = t1 * L * kSlack;
+    if (lo < INFINITY) r.slo = fmaxf(0.f, f32_down(lo));
+    if (hi < INFINITY) r.shi = fminf(r.shi, f32_up(hi));
+    return r;
+}
+
+// First hits (raycast.hip): as ray_child_slabs, and for each child a lower bound of the model parameter s* = t* L of any
+// real hit inside it.  s* lies in the widened interval [n - e, f + e], e = 2^-20 (|n| + |f|) (the derivation above
+// ray_child_line_dist2), so the key is n - e moved towards -inf by 2^-20 of its magnitude, which covers the fp32 roundings
+// of forming it (two in e, one in the difference, one in the move): a positive value shrinks, a negative one grows in
+// magnitude.  tests/csrc/raycast_bound_check.cpp checks key <= t* L on rays through a point of the child.
+__host__ __device__ inline void ray_child_first_key(const NodeV& nd, const RayF& r, bool& h0, bool& h1, float& k0,
+                                                    float& k1) {
+    float n0, f0, n1, f1;
+    ray_child_range(nd, r, n0, f0, n1, f1);
+    const float w = 9.5367431640625e-7f;  // 2^-20
+    const float e0 = w * (fabsf(n0) + fabsf(f0)), e1 = w * (fabsf(n1) + fabsf(f1));
+    h0 = n0 <= f0 + e0;
+    h1 = n1 <= f1 + e1;
+#if defined(MUTATE_RAYCAST_KEY)  // tests/csrc/raycast_bound_check.cpp's sensitivity check: the far end instead
+    k0 = f0;
+    k1 = f1;
+#else
+    const float g0 = n0 - e0, g1 = n1 - e1;
+    k0 = g0 - w * fabsf(g0);
+    k1 = g1 - w * fabsf(g1);
+#endif
 }
 
 // Per-lane traversal stack: entry sp lives in LDS (lds[sp * kBlock], lane-interleaved) for

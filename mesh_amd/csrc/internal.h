@@ -313,6 +313,24 @@ int launch_alongnormal_stats(const msh_tree* tree, const QueryOrder& ord, size_t
 int launch_visibility_stats(const msh_tree* tree, const double* d_cams, size_t C, double min_dist,
                             unsigned long long* d_counts, hipStream_t s);
 
+// ---- ray casting (raycast.hip) ----
+// Caller-order outputs of S rays.  First hit (any == false): t (S,), face (S,), and pt (S,3), w (S,3), which may be
+// nullptr; occlusion (any == true): hit (S,) alone.
+struct RayOut {
+    bool any;
+    double* t;
+    uint32_t* face;
+    double* pt;
+    double* w;
+    uint8_t* hit;
+};
+// ord.q / ord.n: the caller's origins and directions with the slot order of the origins (ord.perm, or identity);
+// d_range: (S,2) caller rows, or nullptr for [0, +inf].  Plain triangle trees; the walks start at the root.  d_stats ==
+// nullptr: the timed query ("raycast" / "occluded").  Otherwise the same walks, untimed, no output written: d_stats[0]
+// += internal nodes loaded, [1] += leaf tests.  Uses ws.counters and ws.spill.  Asynchronous on s.
+int launch_raycast(msh_tree* tree, const QueryOrder& ord, const double* d_range, size_t S, const RayOut& o,
+                   unsigned long long* d_stats, hipStream_t s);
+
 // ---- triangle-triangle (tritri.hip) ----
 // flags[i] = 1 iff query triangle i intersects any tree triangle (self: skip shared-vertex pairs and
 // the query triangles are the tree's own leaves in face order).

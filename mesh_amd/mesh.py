@@ -189,6 +189,17 @@ class Mesh(object):
         use the entry cut, so none is asked for)."""
         return self.compute_aabb_tree().nearest_k(vertices, k, max_distance)
 
+    def ray_cast(self, origins, directions, t_range=None, barycentric=False):
+        """(t (S,), faces (S,) uint32, points (S,3)) of the first hit of every ray `origins[i] + t directions[i]` with
+        this mesh, t in `t_range`; with `barycentric` also the weights (S,3) (search.AabbTree.ray_cast on a tree built
+        for this call; the walk does not use the entry cut, so none is asked for)."""
+        return self.compute_aabb_tree().ray_cast(origins, directions, t_range, barycentric)
+
+    def line_of_sight(self, a, b, margin=0.0):
+        """bool (S,): whether this mesh leaves the segment `a[i] -> b[i]` free between its parameters `margin` and
+        `1 - margin` (search.AabbTree.line_of_sight on a tree built for this call)."""
+        return self.compute_aabb_tree().line_of_sight(a, b, margin)
+
     def signed_distances(self, vertices):
         """Signed distance of every row of `vertices` to this mesh, (S,) float64: negative inside, positive outside
         (search.AabbTree.signed_distance on a tree built for this batch, as closest_faces_and_points builds one).

@@ -72,6 +72,32 @@ class AabbTree(object):
         from . import spatialsearch
         return spatialsearch.aabbtree_nearest_barycentric(self.cpp_handle, _f64c(v_samples))
 
+    def ray_cast(self, origins, directions, t_range=None, barycentric=False):
+        """First hit of every ray ``origins[i] + t directions[i]``, ``t`` in the closed range ``t_range`` (None:
+        ``[0, inf]``; a pair for every row; or (S,2)): (t (S,) f64, face (S,) u32, point (S,3) f64), with
+        ``barycentric=True`` also the weights (S,3) of the point in ``f[face]``.  Directions need not be unit vectors.
+        The smallest (t, face id) wins; a miss gives t = inf, face 0xFFFFFFFF and NaN point and weights."""
+        from . import spatialsearch
+        return spatialsearch.aabbtree_raycast(self.cpp_handle, _f64c(origins), _f64c(directions), t_range, barycentric)
+
+    def occluded(self, origins, directions, t_range=None):
+        """bool (S,): whether each ray meets any face within ``t_range`` (see ``ray_cast``)."""
+        from . import spatialsearch
+        return spatialsearch.aabbtree_occluded(self.cpp_handle, _f64c(origins), _f64c(directions), t_range)
+
+    def line_of_sight(self, a, b, margin=0.0):
+        """bool (S,): True where the segment ``a[i] -> b[i]`` meets no face between its parameters ``margin`` and
+        ``1 - margin`` (0 at ``a``, 1 at ``b``); a positive margin keeps end points that lie on the surface from
+        blocking their own segment."""
+        from . import spatialsearch
+        a, b = _f64c(a), _f64c(b)
+        if a.ndim != 2 or b.ndim != 2 or a.shape[1] != 3 or a.shape != b.shape:
+            raise ValueError("line_of_sight: a and b must both be Nx3")
+        margin = float(margin)
+        if not 0.0 <= margin <= 0.5:
+            raise ValueError("line_of_sight: margin must be in [0, 0.5], got %r" % (margin,))
+        return ~spatialsearch.aabbtree_occluded(self.cpp_handle, a, b - a, (margin, 1.0 - margin))
+
     def orientation_info(self):
         """Topology counters of the mesh as the sign table sees it (built on first use): a dict with
         ``boundary_edges``, ``nonmanifold_edges``, ``inconsistent_edges`` and ``degenerate_faces``.  All zero:

@@ -12,7 +12,8 @@ constructions).  Deliberate differences:
 Beyond the reference: ``aabbtree_intersections_pairs`` / ``aabbtree_selfintersections_pairs`` return which face
 hits which face, as a sorted (K, 2) pair list; ``aabbtree_signed_distance`` and ``aabbtree_winding_number`` answer
 inside / outside, the first on closed manifold meshes, the second on any triangle set; ``aabbtree_nearest_k`` and
-``points_nearest_k`` return the K nearest faces or points of every row, optionally within a radius.
+``points_nearest_k`` return the K nearest faces or points of every row, optionally within a radius;
+``aabbtree_raycast`` and ``aabbtree_occluded`` answer first-hit and occlusion queries for arbitrary rays.
 """
 import numpy as np
 
@@ -202,6 +203,67 @@ def aabbtree_nearest_alongnormal(tree, p, n):
     N.check(N.lib().msh_tree_nearest_alongnormal(tree.ptr, N.dptr(p), N.dptr(n), S, N.dptr(dist), N.uptr(face),
                                                   N.dptr(pt)))
     return dist, face, pt
+
+
+def _ray_args(tree, o, d, t_range, fn):
+    """The validated arguments of a ray query: (tree, origins (S,3), directions (S,3), range (S,2) or None)."""
+    tree = _tree(tree, fn)
+    if not isinstance(o, np.ndarray) or not isinstance(d, np.ndarray):
+        raise TypeError("%s() arguments must be numpy.ndarray" % fn)
+    if o.ndim != 2 or d.ndim != 2 or o.shape[1] != 3 or d.shape[1] != 3 or o.shape[0] != d.shape[0]:
+        raise ValueError("Origins and directions must be Nx3")
+    if tree.kind != "triangles":
+        raise TypeError("%s: handle is not a triangle tree" % fn)
+    S = o.shape[0]
+    rng = None
+    if t_range is not None:
+        r = np.asarray(t_range, dtype=np.float64)
+        if r.shape == (2,):
+            # a pair of scalars for every row: a range no ray can have is the caller's mistake
+            if not r[0] <= r[1]:
+                raise ValueError("%s: t_range must be (t0, t1) with t0 <= t1 (not NaN), got %r" % (fn, t_range))
+            rng = np.empty((S, 2), dtype=np.float64)
+            rng[:] = r
+        elif r.shape == (S, 2):
+            rng = np.ascontiguousarray(r)  # per-row ranges: a NaN or t0 > t1 makes that row a miss
+        else:
+            raise ValueError("%s: t_range must be None, a pair (t0, t1) or an Nx2 array" % fn)
+    return tree, np.ascontiguousarray(o, dtype=np.float64), np.ascontiguousarray(d, dtype=np.float64), rng
+
+
+def aabbtree_raycast(tree, origins, directions, t_range=None, barycentric=False):
+    """(t (S,) float64, face (S,) uint32, point (S,3) float64), and with ``barycentric`` the weights (S,3) float64 of
+    the point in ``f[face]``: the first hit of every ray ``origins[i] + t directions[i]`` with ``t`` in the closed
+    range ``t_range`` (no reference counterpart).
+
+    A direction may have any non-zero length and is used as given.  ``t_range`` is None for ``[0, inf]``, a pair
+    ``(t0, t1)`` for every row, or an (S,2) array; ``t0 < 0`` is taken as 0.  The hit is the lexicographic minimum of
+    (t, face id) over the faces the ray meets (closed ray, closed triangles; a ray lying in a face's plane enters it at
+    the lower end of their overlap), with the predicate and the point construction of
+    ``aabbtree_nearest_alongnormal``.  A miss gives ``t = inf``, face 0xFFFFFFFF and NaN point and weights; so does a
+    row that cannot be cast (non-finite values, a zero direction, a NaN range or ``t0 > t1`` in an array row).  The
+    extra faces of a tree built with them are included, with ids after the main faces."""
+    tree, o, d, rng = _ray_args(tree, origins, directions, t_range, "aabbtree_raycast")
+    S = o.shape[0]
+    specs = [((S,), np.float64), ((S,), np.uint32), ((S, 3), np.float64)]
+    if barycentric:
+        specs.append(((S, 3), np.float64))
+    out = N.empty_results(*specs)
+    N.check(N.lib().msh_tree_raycast(tree.ptr, N.dptr(o), N.dptr(d), N.dptr(rng), S, N.dptr(out[0]), N.uptr(out[1]),
+                                     N.dptr(out[2]), N.dptr(out[3]) if barycentric else None))
+    return tuple(out)
+
+
+def aabbtree_occluded(tree, origins, directions, t_range=None):
+    """bool (S,): whether the ray ``origins[i] + t directions[i]``, ``t`` in ``t_range``, meets any face (the hit set
+    of ``aabbtree_raycast``; the search stops at the first hit it finds).  With ``directions = b - a`` and
+    ``t_range = (0, 1)`` it tells whether the segment a -> b is blocked."""
+    tree, o, d, rng = _ray_args(tree, origins, directions, t_range, "aabbtree_occluded")
+    S = o.shape[0]
+    hit, = N.empty_results(((S,), np.uint8))
+    N.check(N.lib().msh_tree_occluded(tree.ptr, N.dptr(o), N.dptr(d), N.dptr(rng), S,
+                                      hit.ctypes.data_as(N.ctypes.POINTER(N.ctypes.c_uint8))))
+    return hit.astype(bool)
 
 
 def aabbtree_intersections_indices(tree, qv, qf):
