@@ -471,6 +471,46 @@ int msh_tree_occluded_device(msh_tree* tree, const double* d_o, const double* d_
 int msh_tree_raycast_stats(msh_tree* tree, const double* d_o, const double* d_d, const double* d_range, size_t S,
                            int any, uint64_t* nodes, uint64_t* leaves);
 
+/* ---- ray casting on plain triangle trees: hit counts and sorted all-hits lists ----
+ * Rows, ranges, castability and the hit set are exactly those of msh_tree_raycast above: row i is (o, d, [t0, t1]), d used
+ * as given, t0 < 0 taken as 0; face j is in the hit set when the predicate reports a proper hit with t0 <= t_j <= t1
+ * (t_j not NaN) or a coplanar overlap with a non-empty clipped interval (t_j: its lower end); a row that cannot be cast
+ * has an empty hit set and is no error; the extra faces of msh_tree_build_ex are included with ids [T, T + ET).
+ *   counts  msh_tree_raycast_count: count (S,) u32, count[i] the size of row i's hit set.
+ *   lists   msh_tree_raycast_all: the hits of all rows as CSR.  counts (S,) u32 (may be NULL) is as above and its
+ *           exclusive scan indexes the list; the list is sorted by (row, t by value, face id): -0.0 == 0.0, and equal t --
+ *           shared edges and vertices, duplicated faces -- goes to the smaller face id.  t[k] is the value the predicate
+ *           produced, unchanged; face[k] its face id; pt (cap,3) (may be NULL) is msh_tree_raycast's construction:
+ *           CGAL's plane / line intersection for a proper hit, o + t d for a coplanar hit or a zero denominator; side (cap,)
+ *           i8 (may be NULL) is +1 where den = n . d < 0 (the ray meets the front of the face, n = (b - a) x (c - a) in the
+ *           order of f[face]), -1 where den > 0, 0 for a coplanar hit.
+ *           So the first entry of every non-empty row equals msh_tree_raycast's (t, face, pt) bit for bit, and count > 0
+ *           equals msh_tree_occluded.
+ * Cap protocol (that of the pair lists): *K always receives the full number of hits; the first min(K, cap) entries in
+ * sorted order are written; cap == 0 with NULL list pointers counts only (nothing is filled or ordered); counts is
+ * always complete; K > 2^32 - 1 is MSH_EINVAL, found by a 64-bit sum; S == 0 is MSH_OK with K = 0.
+ * Determinism: a row's count and list are a function of (tree, o, d, range) alone -- not of the other rows, their order
+ * or the chunking; the same inputs give the same bytes on every call; no atomic decides content or order.
+ * Plain triangle trees only: normals-metric, point and batched trees and NULL handles are MSH_EINVAL, checked in the
+ * order handle, tree kind, row count, pointers.  The walk is msh_tree_occluded's without the early exit (nothing can be
+ * pruned by a best t); the list call walks twice (count, fill) and orders each row's hits: rows of at most 32 hits in
+ * their own lane, longer ones through radix sorts of all K entries.
+ * msh_tree_raycast_count goes through the pinned-slab pipeline and splits its rows over the handle's replicas;
+ * msh_tree_raycast_all stays on the handle's own device (the rays are uploaded whole; counts and the first min(K, cap)
+ * entries come back).  The *_device forms take device pointers and are asynchronous on `stream`, except that
+ * msh_tree_raycast_all_device waits for the read-back of K.
+ * msh_timing_get names: "raycast_count", "raycast_scan", "raycast_fill", "raycast_order" (long rows only),
+ * "raycast_emit". */
+int msh_tree_raycast_count(msh_tree* tree, const double* o, const double* d, const double* range, size_t S,
+                           uint32_t* count);
+int msh_tree_raycast_count_device(msh_tree* tree, const double* d_o, const double* d_d, const double* d_range, size_t S,
+                                  uint32_t* d_count, void* stream);
+int msh_tree_raycast_all(msh_tree* tree, const double* o, const double* d, const double* range, size_t S,
+                         uint32_t* counts, double* t, uint32_t* face, double* pt, int8_t* side, size_t cap, size_t* K);
+int msh_tree_raycast_all_device(msh_tree* tree, const double* d_o, const double* d_d, const double* d_range, size_t S,
+                                uint32_t* d_counts, double* d_t, uint32_t* d_face, double* d_pt, int8_t* d_side,
+                                size_t cap, size_t* K, void* stream);
+
 /* ---- multi-GPU replication (RCCL broadcast of a built BVH over xGMI) ---- */
 /* Size of the flat device blob holding the mesh + BVH of a handle. */
 int msh_tree_blob_size(const msh_tree* tree, size_t* bytes);

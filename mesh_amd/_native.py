@@ -93,6 +93,12 @@ SIGNATURES = [
     ("msh_tree_occluded", _i, [_vp, _c_double_p, _c_double_p, _c_double_p, _sz, ctypes.POINTER(ctypes.c_uint8)]),
     ("msh_tree_occluded_device", _i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     ("msh_tree_raycast_stats", _i, [_vp, _vp, _vp, _vp, _sz, _i, _c_u64_p, _c_u64_p]),
+    ("msh_tree_raycast_count", _i, [_vp, _c_double_p, _c_double_p, _c_double_p, _sz, _c_u32_p]),
+    ("msh_tree_raycast_count_device", _i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("msh_tree_raycast_all", _i, [_vp, _c_double_p, _c_double_p, _c_double_p, _sz, _c_u32_p, _c_double_p, _c_u32_p,
+                                  _c_double_p, ctypes.POINTER(ctypes.c_int8), _sz, ctypes.POINTER(_sz)]),
+    ("msh_tree_raycast_all_device", _i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.POINTER(_sz),
+                                         _vp]),
     ("msh_tree_blob_size", _i, [_vp, ctypes.POINTER(_sz)]),
     ("msh_tree_blob_pack", _i, [_vp, _vp, _vp]),
     ("msh_tree_blob_unpack", _i, [_vp, _sz, _i, _vp, ctypes.POINTER(_vp)]),
@@ -406,7 +412,7 @@ def source_build_id(extra=""):
     import os
     csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
     names = sorted(["sort.hip", "build.hip", "refine.hip", "nearest.hip", "cutbuild.hip", "rays.hip", "tritri.hip", "geometry.hip",
-                    "sign.hip", "winding.hip", "kbest.hip", "raycast.hip", "api.cpp", "devmem.cpp", "hostpipe.cpp", "entrycut.cpp", "blob.cpp",
+                    "sign.hip", "winding.hip", "kbest.hip", "raycast.hip", "raycast_all.hip", "api.cpp", "devmem.cpp", "hostpipe.cpp", "entrycut.cpp", "blob.cpp",
                     "hostpipe.h", "hostplan.h", "loaders.cpp", "common.h", "internal.h", "knn.h", "rays.h"])
     h = hashlib.sha256()
     for p in [os.path.join(csrc, n) for n in names] + [os.path.join(csrc, "..", "..", "include", "meshsearch.h")]:

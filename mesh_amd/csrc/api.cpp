@@ -1068,6 +1068,138 @@ int msh_tree_raycast_stats(msh_tree* t, const double* d_o, const double* d_d, co
     return MSH_OK;
 }
 
+// ---- ray casting: hit counts and sorted all-hits lists (raycast_all.hip) ----
+
+static int raycast_count_run(msh_tree* t, const double* d_o, const double* d_d, const double* d_range, size_t S,
+                             uint32_t* d_count, hipStream_t s) {
+    WsOrder order(t, s);
+    QueryOrder ord;
+    MSH_TRY(sort_queries(t, d_o, d_d, S, s, &ord, true));
+    return launch_raycast_count(t, ord, d_range, S, d_count, s);
+}
+
+int msh_tree_raycast_count_device(msh_tree* t, const double* d_o, const double* d_d, const double* d_range, size_t S,
+                                  uint32_t* d_count, void* stream) {
+    MSH_TRY(check_plain_tree(t, kTriangles, "msh_tree_raycast_count_device", "ray casting needs"));
+    MSH_TRY(check_count(S, "msh_tree_raycast_count_device"));
+    if (S == 0) return MSH_OK;
+    if (!d_o || !d_d || !d_count) { set_error("msh_tree_raycast_count_device: null argument"); return MSH_EINVAL; }
+    return raycast_count_run(t, d_o, d_d, d_range, S, d_count, pick(t, stream));
+}
+
+int msh_tree_raycast_count(msh_tree* t, const double* o, const double* d, const double* range, size_t S,
+                           uint32_t* count) {
+    MSH_TRY(check_plain_tree(t, kTriangles, "msh_tree_raycast_count", "ray casting needs"));
+    MSH_TRY(check_count(S, "msh_tree_raycast_count"));
+    if (S == 0) return MSH_OK;
+    if (!o || !d || !count) { set_error("msh_tree_raycast_count: null argument"); return MSH_EINVAL; }
+    HostCols c;
+    const auto co = c.in(o, 3), cd = c.in(d, 3);
+    const auto cr = c.in(range, range ? 2 : 0);
+    const auto ccount = c.out(count, 1);
+    return host_call(t, S, c, kNoCut, [&](msh_tree* h, size_t n, const Slabs& s) {
+        return raycast_count_run(h, s[co], s[cd], range ? s[cr] : nullptr, n, s[ccount], h->stream);
+    });
+}
+
+// Count, read K back, then scan / fill / order / emit the first min(K, cap) entries (launch_raycast_all_*).  host_out:
+// the outputs are host arrays -- the list comes through device buffers of its own and the call returns after the
+// download; otherwise they are device arrays and everything after the read-back of K is left queued on s.
+static int raycast_all_run(msh_tree* t, const double* d_o, const double* d_d, const double* d_range, size_t S,
+                           bool host_out, uint32_t* counts, const HitOut& out, size_t cap, size_t* K, hipStream_t s,
+                           const char* fn) {
+    DevBuf dt, dface, dpt, dside;
+    int st = MSH_OK;
+    do {
+        WsOrder order(t, s);
+        QueryOrder ord;
+        if ((st = sort_queries(t, d_o, d_d, S, s, &ord, true)) != MSH_OK) break;
+        HitTotals tot{};
+        if ((st = launch_raycast_all_count(t, ord, d_range, S, &tot, s)) != MSH_OK) break;
+        // the 64-bit sum is the detector: the 32-bit scan below is never run on counts it would wrap on
+        if (tot.K > 0xFFFFFFFFull) {
+            set_error("%s: %llu hits exceed the 32-bit offset range of one call (split the rays)", fn,
+                      (unsigned long long)tot.K);
+            st = MSH_EINVAL;
+            break;
+        }
+        *K = (size_t)tot.K;
+        const size_t n = std::min<size_t>((size_t)tot.K, cap);
+        HitOut d = out;
+        if (host_out && n) {
+            if ((st = dt.reserve(n * sizeof(double))) != MSH_OK) break;
+            if ((st = dface.reserve(n * sizeof(uint32_t))) != MSH_OK) break;
+            if (out.pt && (st = dpt.reserve(3 * n * sizeof(double))) != MSH_OK) break;
+            if (out.side && (st = dside.reserve(n * sizeof(int8_t))) != MSH_OK) break;
+            d = HitOut{dt.as<double>(), dface.as<uint32_t>(), out.pt ? dpt.as<double>() : nullptr,
+                       out.side ? dside.as<int8_t>() : nullptr};
+        }
+        if ((st = launch_raycast_all_emit(t, ord, d_range, S, tot, d, n, s)) != MSH_OK) break;
+        hipError_t e = hipSuccess;
+        const hipMemcpyKind kind = host_out ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        if (counts) e = hipMemcpyAsync(counts, t->ws.flags.ptr, S * sizeof(uint32_t), kind, s);
+        if (host_out && n) {
+            if (e == hipSuccess) e = hipMemcpyAsync(out.t, d.t, n * sizeof(double), hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(out.face, d.face, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess && out.pt)
+                e = hipMemcpyAsync(out.pt, d.pt, 3 * n * sizeof(double), hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess && out.side)
+                e = hipMemcpyAsync(out.side, d.side, n * sizeof(int8_t), hipMemcpyDeviceToHost, s);
+        }
+        if (e == hipSuccess && host_out) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            set_error("%s: %s", fn, hipGetErrorString(e));
+            st = MSH_EDEVICE;
+        }
+    } while (0);
+    if (host_out || st != MSH_OK) (void)hipStreamSynchronize(s);
+    dt.release(); dface.release(); dpt.release(); dside.release();
+    return st;
+}
+
+static int check_raycast_all(msh_tree* t, size_t S, const double* tt, const uint32_t* face, const double* pt,
+                             const int8_t* side, size_t cap, size_t* K, const char* fn) {
+    MSH_TRY(check_plain_tree(t, kTriangles, fn, "ray casting needs"));
+    MSH_TRY(check_count(S, fn));
+    if (!K || (cap && (!tt || !face))) {
+        set_error("%s: null argument", fn);
+        return MSH_EINVAL;
+    }
+    *K = 0;
+    return MSH_OK;
+}
+
+int msh_tree_raycast_all_device(msh_tree* t, const double* d_o, const double* d_d, const double* d_range, size_t S,
+                                uint32_t* d_counts, double* d_t, uint32_t* d_face, double* d_pt, int8_t* d_side,
+                                size_t cap, size_t* K, void* stream) {
+    const char* fn = "msh_tree_raycast_all_device";
+    MSH_TRY(check_raycast_all(t, S, d_t, d_face, d_pt, d_side, cap, K, fn));
+    if (S == 0) return MSH_OK;
+    if (!d_o || !d_d) { set_error("%s: null argument", fn); return MSH_EINVAL; }
+    return raycast_all_run(t, d_o, d_d, d_range, S, false, d_counts, HitOut{d_t, d_face, d_pt, d_side}, cap, K,
+                           pick(t, stream), fn);
+}
+
+int msh_tree_raycast_all(msh_tree* t, const double* o, const double* d, const double* range, size_t S, uint32_t* counts,
+                         double* tt, uint32_t* face, double* pt, int8_t* side, size_t cap, size_t* K) {
+    const char* fn = "msh_tree_raycast_all";
+    MSH_TRY(check_raycast_all(t, S, tt, face, pt, side, cap, K, fn));
+    if (S == 0) return MSH_OK;
+    if (!o || !d) { set_error("%s: null argument", fn); return MSH_EINVAL; }
+    // the list stays on the handle's own device, as the pair lists do: the rays are uploaded whole
+    hipStream_t s = t->stream;
+    DevBuf dov, ddv, drv;
+    int st = upload(dov, o, 3 * S, s);
+    if (st == MSH_OK) st = upload(ddv, d, 3 * S, s);
+    if (st == MSH_OK && range) st = upload(drv, range, 2 * S, s);
+    if (st == MSH_OK)
+        st = raycast_all_run(t, dov.as<double>(), ddv.as<double>(), range ? drv.as<double>() : nullptr, S, true, counts,
+                             HitOut{tt, face, pt, side}, cap, K, s, fn);
+    (void)hipStreamSynchronize(s);
+    dov.release(); ddv.release(); drv.release();
+    return st;
+}
+
 static void host_tris(const double* v, const uint32_t* f, size_t T, std::vector<TriRec>& out) {
     out.resize(T);
     for (size_t t = 0; t < T; ++t) {

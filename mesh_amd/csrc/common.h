@@ -561,6 +561,20 @@ __host__ __device__ inline void ray_child_first_key(const NodeV& nd, const RayF&
 #endif
 }
 
+// All-hits lists (raycast_all.hip): the radix key of a hit parameter t >= 0 (+inf included, never NaN).  The bit pattern
+// of a non-negative double is monotone in its value, and t + 0.0 folds -0.0 onto +0.0, which compare equal.
+// tests/csrc/raycast_all_key_check.cpp checks both.
+__host__ __device__ inline unsigned long long allhits_t_key(double t) {
+#if defined(MUTATE_ALLHITS_KEY)  // the key check's sensitivity build: the raw bits, which put -0.0 after +inf
+    const double z = t;
+#else
+    const double z = t + 0.0;
+#endif
+    unsigned long long u;
+    __builtin_memcpy(&u, &z, sizeof(u));
+    return u;
+}
+
 // Per-lane traversal stack: entry sp lives in LDS (lds[sp * kBlock], lane-interleaved) for
 // sp < kStack and in the block's global spill area beyond.  The spill side uses the nontemporal
 // builtins so the compiler cannot fold the two cases into one generic (flat) access through a

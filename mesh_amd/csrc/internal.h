@@ -331,7 +331,38 @@ struct RayOut {
 int launch_raycast(msh_tree* tree, const QueryOrder& ord, const double* d_range, size_t S, const RayOut& o,
                    unsigned long long* d_stats, hipStream_t s);
 
+// ---- ray casting, all hits (raycast_all.hip) ----
+// d_counts[r] = the size of row r's hit set (launch_raycast's rows, ranges and hit set).  Uses ws.counters and ws.spill.
+// Asynchronous on s; msh_timing_get name "raycast_count".
+int launch_raycast_count(msh_tree* tree, const QueryOrder& ord, const double* d_range, size_t S, uint32_t* d_counts,
+                         hipStream_t s);
+// The hit lists as CSR, sorted by (row, t by value, face id), in the two steps of the pair lists:
+//   count  launch_raycast_count into ws.flags (the counts stay valid until emit) and their totals, read back on s
+//          (synchronous);
+//   emit   scan, fill, order, emit: the first n_emit <= K entries in sorted order to o (t and face; pt (n_emit,3) and
+//          side (n_emit,) may be nullptr); asynchronous on s.  K <= 2^32 - 1.  When no row is longer than kLaneSort the
+//          fill lanes order their own rows; otherwise all K entries go through stable radix sorts (face, t, row).
+// ord must stay valid between the two (ws.vals holds its permutation).  Uses ws.flags, ranges, stats, out_a, out_b,
+// out_c, and for long rows keys, keys_alt, out_d, hist, scan.
+struct HitTotals {
+    uint64_t K;        // 64-bit sum of the counts
+    uint64_t longest;  // the largest count
+};
+struct HitOut {
+    double* t;
+    uint32_t* face;
+    double* pt;
+    int8_t* side;
+};
+int launch_raycast_all_count(msh_tree* tree, const QueryOrder& ord, const double* d_range, size_t S, HitTotals* out,
+                             hipStream_t s);
+int launch_raycast_all_emit(msh_tree* tree, const QueryOrder& ord, const double* d_range, size_t S, const HitTotals& tot,
+                            const HitOut& o, size_t n_emit, hipStream_t s);
+
 // ---- triangle-triangle (tritri.hip) ----
+constexpr int kLaneSort = 32;  // rows of up to this many hits are ordered by their own lane (k_tritri_all, k_raycast_all)
+// out[0] += the 64-bit sum of counts[0..n), out[1] = max(out[1], the largest count); out zeroed by the caller
+int sum_counts(const uint32_t* d_counts, size_t n, unsigned long long* d_out, unsigned nblk, hipStream_t s);
 // flags[i] = 1 iff query triangle i intersects any tree triangle (self: skip shared-vertex pairs and
 // the query triangles are the tree's own leaves in face order).
 int launch_tri_intersect(const msh_tree* tree, const TriRec* d_qtris, size_t Tq, int self_mode, uint32_t* d_flags,

@@ -163,7 +163,6 @@ __device__ inline bool obb_overlap(const TriProj& p, const float* ext) {
 // once, under its smaller face, and the predicate gets the smaller face first; the any-hit mode keeps every leaf, since
 // a face is flagged whatever the id order).  Nothing but a row's own lane writes its count or its segment, so the
 // output does not depend on how lanes are scheduled.
-constexpr int kLaneSort = 32;  // rows of up to this many hits are ordered by their own lane (k_tritri_all)
 enum { kTriAny = 0, kTriCount = 1, kTriFill = 2 };
 
 struct PairArgs {
@@ -308,6 +307,12 @@ __global__ __launch_bounds__(kBlock) void k_sum_counts(const uint32_t* __restric
         atomicAdd(out, sh[0]);
         atomicMax(out + 1, shm[0]);
     }
+}
+
+int sum_counts(const uint32_t* d_counts, size_t n, unsigned long long* d_out, unsigned nblk, hipStream_t s) {
+    k_sum_counts<<<std::max(std::min(nblk, 1024u), 1u), kBlock, 0, s>>>(d_counts, n, d_out);
+    MSH_HIP(hipGetLastError());
+    return MSH_OK;
 }
 
 // pairs (n, 2) row-major from the sorted (row, mesh face) columns

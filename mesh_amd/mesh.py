@@ -195,6 +195,11 @@ class Mesh(object):
         for this call; the walk does not use the entry cut, so none is asked for)."""
         return self.compute_aabb_tree().ray_cast(origins, directions, t_range, barycentric)
 
+    def ray_cast_all(self, origins, directions, t_range=None, points=False, sides=False):
+        """(counts (S,) uint32, t (K,), faces (K,) uint32[, points (K,3)][, sides (K,) int8]): every hit of every ray
+        with this mesh, as CSR sorted by (row, t, face) (search.AabbTree.ray_cast_all on a tree built for this call)."""
+        return self.compute_aabb_tree().ray_cast_all(origins, directions, t_range, points, sides)
+
     def line_of_sight(self, a, b, margin=0.0):
         """bool (S,): whether this mesh leaves the segment `a[i] -> b[i]` free between its parameters `margin` and
         `1 - margin` (search.AabbTree.line_of_sight on a tree built for this call)."""

@@ -85,6 +85,20 @@ class AabbTree(object):
         from . import spatialsearch
         return spatialsearch.aabbtree_occluded(self.cpp_handle, _f64c(origins), _f64c(directions), t_range)
 
+    def ray_count(self, origins, directions, t_range=None):
+        """uint32 (S,): how many faces each ray meets within ``t_range`` (see ``ray_cast``)."""
+        from . import spatialsearch
+        return spatialsearch.aabbtree_raycast_count(self.cpp_handle, _f64c(origins), _f64c(directions), t_range)
+
+    def ray_cast_all(self, origins, directions, t_range=None, points=False, sides=False):
+        """Every hit of every ray, as CSR: (counts (S,) u32, t (K,) f64, face (K,) u32), with ``points=True`` also the
+        hit points (K,3) and with ``sides=True`` the side (K,) i8 each face is met from (+1 front, -1 back, 0 in its
+        plane).  The exclusive scan of ``counts`` indexes the lists; a row's hits are sorted by (t, face id), so its
+        first entry is ``ray_cast``'s answer."""
+        from . import spatialsearch
+        return spatialsearch.aabbtree_raycast_all(self.cpp_handle, _f64c(origins), _f64c(directions), t_range, points,
+                                                  sides)
+
     def line_of_sight(self, a, b, margin=0.0):
         """bool (S,): True where the segment ``a[i] -> b[i]`` meets no face between its parameters ``margin`` and
         ``1 - margin`` (0 at ``a``, 1 at ``b``); a positive margin keeps end points that lie on the surface from

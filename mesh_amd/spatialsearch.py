@@ -13,7 +13,8 @@ Beyond the reference: ``aabbtree_intersections_pairs`` / ``aabbtree_selfintersec
 hits which face, as a sorted (K, 2) pair list; ``aabbtree_signed_distance`` and ``aabbtree_winding_number`` answer
 inside / outside, the first on closed manifold meshes, the second on any triangle set; ``aabbtree_nearest_k`` and
 ``points_nearest_k`` return the K nearest faces or points of every row, optionally within a radius;
-``aabbtree_raycast`` and ``aabbtree_occluded`` answer first-hit and occlusion queries for arbitrary rays.
+``aabbtree_raycast`` and ``aabbtree_occluded`` answer first-hit and occlusion queries for arbitrary rays,
+``aabbtree_raycast_count`` and ``aabbtree_raycast_all`` return how many faces each ray meets and all of them in order.
 """
 import numpy as np
 
@@ -264,6 +265,47 @@ def aabbtree_occluded(tree, origins, directions, t_range=None):
     N.check(N.lib().msh_tree_occluded(tree.ptr, N.dptr(o), N.dptr(d), N.dptr(rng), S,
                                       hit.ctypes.data_as(N.ctypes.POINTER(N.ctypes.c_uint8))))
     return hit.astype(bool)
+
+
+def aabbtree_raycast_count(tree, origins, directions, t_range=None):
+    """counts (S,) uint32: how many faces each ray ``origins[i] + t directions[i]``, ``t`` in ``t_range``, meets -- the
+    size of the hit set of ``aabbtree_raycast`` (no reference counterpart).  ``counts > 0`` is ``aabbtree_occluded``."""
+    tree, o, d, rng = _ray_args(tree, origins, directions, t_range, "aabbtree_raycast_count")
+    S = o.shape[0]
+    counts, = N.empty_results(((S,), np.uint32))
+    N.check(N.lib().msh_tree_raycast_count(tree.ptr, N.dptr(o), N.dptr(d), N.dptr(rng), S, N.uptr(counts)))
+    return counts
+
+
+def aabbtree_raycast_all(tree, origins, directions, t_range=None, points=False, sides=False):
+    """(counts (S,) uint32, t (K,) float64, face (K,) uint32[, point (K,3) float64][, side (K,) int8]): every hit of
+    every ray, as CSR -- the exclusive scan of ``counts`` indexes the lists (no reference counterpart).
+
+    Rays, ranges and the hit set are ``aabbtree_raycast``'s.  The list is sorted by (row, t, face id): ``t`` is
+    compared by value and equal ``t`` (shared edges and vertices, duplicated faces) goes to the smaller face id, so
+    the first entry of every non-empty row is ``aabbtree_raycast``'s answer bit for bit.  ``point`` is that function's
+    construction; ``side`` is +1 where the ray meets the front of the face (against the normal of ``f[face]``), -1
+    where it meets the back, 0 for a ray lying in the face's plane.  A row that cannot be cast has no hits."""
+    tree, o, d, rng = _ray_args(tree, origins, directions, t_range, "aabbtree_raycast_all")
+    S = o.shape[0]
+    fn = N.lib().msh_tree_raycast_all
+    i8p = N.ctypes.POINTER(N.ctypes.c_int8)
+    counts = np.empty(S, dtype=np.uint32)
+    K = N._sz(0)
+
+    def call(cap):
+        out = [np.empty(cap, dtype=np.float64), np.empty(cap, dtype=np.uint32),
+               np.empty((cap, 3), dtype=np.float64) if points else None, np.empty(cap, dtype=np.int8) if sides else None]
+        N.check(fn(tree.ptr, N.dptr(o), N.dptr(d), N.dptr(rng), S, N.uptr(counts), N.dptr(out[0]), N.uptr(out[1]),
+                   N.dptr(out[2]), out[3].ctypes.data_as(i8p) if sides else None, cap, N.ctypes.byref(K)))
+        return out
+
+    # one call with a first guess at the capacity, a second with cap = K only when K > cap (as _pairs_call)
+    cap = _first_cap(S)
+    out = call(cap)
+    if K.value > cap:
+        out = call(K.value)
+    return (counts,) + tuple(x[:K.value].copy() for x in out if x is not None)
 
 
 def aabbtree_intersections_indices(tree, qv, qf):
