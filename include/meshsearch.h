@@ -425,6 +425,58 @@ int msh_tree_knearest_device(msh_tree* tree, const double* d_q, size_t S, uint32
  * [2] list insertions, [3] deepest stack any row reached (entries).  d_q is a device pointer; synchronous. */
 int msh_tree_knearest_stats(msh_tree* tree, const double* d_q, size_t S, uint32_t K, double r_max, uint64_t counts[4]);
 
+/* ---- all primitives within a radius (scipy's query_ball_point) on point trees and plain triangle trees ----
+ * Row i is a point q_i and a radius r_i.  A primitive (a vertex of a point tree; a leaf triangle of a triangle tree, the
+ * extra faces of msh_tree_build_ex included) qualifies when d2 <= r2_i: d2 exactly the fp64 squared distance of the
+ * K-nearest queries above, r2_i = r_i * r_i rounded once in fp64.  r = +inf takes every primitive, r = 0 exact hits only.
+ *   radius  double r_max and const double* r_rows (S,): r_rows == NULL uses r_max for every row; otherwise r_rows[i] is
+ *           used and r_max is ignored.  A scalar r_max that is negative or NaN is MSH_EINVAL, checked before the handle.
+ *           A per-row radius that is negative or NaN gives that row count 0, as does a non-finite q_i; neither is an error.
+ *   counts  msh_points_within_count, msh_tree_within_count: count (S,) u32, count[i] the number of qualifying primitives.
+ *   lists   msh_points_within, msh_tree_within: the neighbours of all rows as CSR.  counts (S,) u32 (may be NULL) is as
+ *           above and its exclusive scan indexes the lists; entries are sorted by (row, d2, id).  idx / face (cap,) u32 is
+ *           the vertex index or face id, dist (cap,) f64 = sqrt(d2); for triangle trees pt (cap,3) f64 and part (cap,)
+ *           u32 (each may be NULL) are the closest point and its part code by msh_tree_knearest's construction.
+ *           So for every K' <= MSH_KNEAREST_MAX the first min(K', count[i]) entries of row i equal row i of
+ *           msh_*_knearest(K', r_i) in id, dist, pt and part bit for bit, and min(count[i], K') is its count; with
+ *           r = +inf entry 0 equals msh_points_nearest / msh_tree_nearest.
+ * Cap protocol (that of msh_tree_raycast_all): *K always receives the full number of entries; the first min(K, cap)
+ * entries in sorted order are written; cap == 0 with NULL list pointers counts only (nothing is filled or ordered);
+ * counts is always complete; K > 2^32 - 1 is MSH_EINVAL, found by a 64-bit sum; S == 0 is MSH_OK with K = 0.
+ * Determinism: a row's count and list are a function of (tree, q_i, r_i) alone -- not of the other rows, their order or
+ * the chunking; the same inputs give the same bytes on every call; no atomic decides content or order.
+ * msh_points_* take point trees, msh_tree_within* plain triangle trees: normals-metric and batched trees and NULL handles
+ * are MSH_EINVAL, checked in the order handle, tree kind, row count, pointers.  The walk is msh_*_knearest's with the
+ * radius as its only bound; the list call walks twice (count, fill) and orders each row: rows of at most 32 entries in
+ * their own lane, longer ones through radix sorts of all K entries.
+ * The counts calls go through the pinned-slab pipeline and split their rows over the handle's replicas; the list calls
+ * stay on the handle's own device (the rows are uploaded whole; counts and the first min(K, cap) entries come back).
+ * The *_device forms take device pointers (d_r_rows too) and are asynchronous on `stream`, except that the list calls
+ * wait for the read-back of K.
+ * msh_timing_get names: "within_count", "within_scan", "within_fill", "within_order" (long rows only), "within_emit". */
+int msh_points_within_count(msh_tree* tree, const double* q, size_t S, double r_max, const double* r_rows,
+                            uint32_t* count);
+int msh_points_within_count_device(msh_tree* tree, const double* d_q, size_t S, double r_max, const double* d_r_rows,
+                                   uint32_t* d_count, void* stream);
+int msh_tree_within_count(msh_tree* tree, const double* q, size_t S, double r_max, const double* r_rows,
+                          uint32_t* count);
+int msh_tree_within_count_device(msh_tree* tree, const double* d_q, size_t S, double r_max, const double* d_r_rows,
+                                 uint32_t* d_count, void* stream);
+int msh_points_within(msh_tree* tree, const double* q, size_t S, double r_max, const double* r_rows, uint32_t* counts,
+                      uint32_t* idx, double* dist, size_t cap, size_t* K);
+int msh_points_within_device(msh_tree* tree, const double* d_q, size_t S, double r_max, const double* d_r_rows,
+                             uint32_t* d_counts, uint32_t* d_idx, double* d_dist, size_t cap, size_t* K, void* stream);
+int msh_tree_within(msh_tree* tree, const double* q, size_t S, double r_max, const double* r_rows, uint32_t* counts,
+                    uint32_t* face, double* dist, double* pt, uint32_t* part, size_t cap, size_t* K);
+int msh_tree_within_device(msh_tree* tree, const double* d_q, size_t S, double r_max, const double* d_r_rows,
+                           uint32_t* d_counts, uint32_t* d_face, double* d_dist, double* d_pt, uint32_t* d_part,
+                           size_t cap, size_t* K, void* stream);
+/* untimed, the count walk, point trees and plain triangle trees: counts[0] nodes visited, [1] primitives evaluated,
+ * [2] entries (the sum of the rows' counts), [3] deepest stack any row reached.  d_q and d_r_rows are device pointers;
+ * synchronous. */
+int msh_tree_within_stats(msh_tree* tree, const double* d_q, size_t S, double r_max, const double* d_r_rows,
+                          uint64_t counts[4]);
+
 /* ---- ray casting on plain triangle trees: first hit and occlusion for arbitrary rays ----
  * Row i is an origin o, a direction d and a closed range [t0, t1] of the parameter t of the point o + t d.  d may have
  * any non-zero length and is used as given (no (o + d) - o as for a CGAL Ray_3).  range is (S,2), or NULL for

@@ -87,6 +87,19 @@ SIGNATURES = [
                                _c_double_p, _c_u32_p, _c_u32_p]),
     ("msh_tree_knearest_device", _i, [_vp, _vp, _sz, ctypes.c_uint32, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("msh_tree_knearest_stats", _i, [_vp, _vp, _sz, ctypes.c_uint32, ctypes.c_double, _c_u64_p]),
+    ("msh_points_within_count", _i, [_vp, _c_double_p, _sz, ctypes.c_double, _c_double_p, _c_u32_p]),
+    ("msh_points_within_count_device", _i, [_vp, _vp, _sz, ctypes.c_double, _vp, _vp, _vp]),
+    ("msh_tree_within_count", _i, [_vp, _c_double_p, _sz, ctypes.c_double, _c_double_p, _c_u32_p]),
+    ("msh_tree_within_count_device", _i, [_vp, _vp, _sz, ctypes.c_double, _vp, _vp, _vp]),
+    ("msh_points_within", _i, [_vp, _c_double_p, _sz, ctypes.c_double, _c_double_p, _c_u32_p, _c_u32_p, _c_double_p,
+                               _sz, ctypes.POINTER(_sz)]),
+    ("msh_points_within_device", _i, [_vp, _vp, _sz, ctypes.c_double, _vp, _vp, _vp, _vp, _sz, ctypes.POINTER(_sz),
+                                      _vp]),
+    ("msh_tree_within", _i, [_vp, _c_double_p, _sz, ctypes.c_double, _c_double_p, _c_u32_p, _c_u32_p, _c_double_p,
+                             _c_double_p, _c_u32_p, _sz, ctypes.POINTER(_sz)]),
+    ("msh_tree_within_device", _i, [_vp, _vp, _sz, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                    ctypes.POINTER(_sz), _vp]),
+    ("msh_tree_within_stats", _i, [_vp, _vp, _sz, ctypes.c_double, _vp, _c_u64_p]),
     ("msh_tree_raycast", _i, [_vp, _c_double_p, _c_double_p, _c_double_p, _sz, _c_double_p, _c_u32_p, _c_double_p,
                               _c_double_p]),
     ("msh_tree_raycast_device", _i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
@@ -177,6 +190,21 @@ def check_knearest(k, max_distance, what):
     if not r >= 0.0:
         raise ValueError("%s: the distance cap must be >= 0 (inf: none), got %r" % (what, max_distance))
     return int(k), r
+
+
+def check_within(r, S, what):
+    """(r_max, r_rows) of a radius query of S rows as the C ABI takes them: a scalar r gives (float(r), None), ValueError
+    when it is negative or NaN; an (S,) array gives (0.0, its float64 C-contiguous copy), whose negative or NaN entries
+    are legal (those rows are empty).  Any other shape is a ValueError.  Before any device work."""
+    a = np.asarray(r, dtype=np.float64)
+    if a.ndim == 0:
+        r = float(a)
+        if not r >= 0.0:
+            raise ValueError("%s: the radius must be >= 0 (inf: every primitive), got %r" % (what, r))
+        return r, None
+    if a.shape != (int(S),):
+        raise ValueError("%s: r must be a scalar or of shape (%d,), got %r" % (what, int(S), a.shape))
+    return 0.0, np.ascontiguousarray(a)
 
 
 def _preload_single_hip_runtime():
@@ -378,6 +406,15 @@ class Handle(object):
         check(lib().msh_tree_knearest_stats(self.ptr, _vp(d_q), int(S), k, r, out))
         return tuple(int(x) for x in out)
 
+    def within_stats(self, d_q, S, r, d_r_rows=None):
+        """msh_tree_within_stats on S device rows at address d_q with the scalar radius r, or the per-row radii at
+        device address d_r_rows (point and plain triangle trees) -> (nodes visited, primitives evaluated, entries,
+        deepest stack any row reached); untimed, the count walk of the query."""
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().msh_tree_within_stats(self.ptr, _vp(d_q), int(S), float(r), _vp(d_r_rows) if d_r_rows else None,
+                                          out))
+        return tuple(int(x) for x in out)
+
     def raycast_stats(self, d_o, d_d, S, d_range=None, any_hit=False):
         """msh_tree_raycast_stats on S device rays at addresses d_o, d_d (and d_range, or None) -> (internal nodes
         loaded, leaf tests) of the first-hit walks, or with any_hit of the occlusion walks; untimed, nothing written."""
@@ -412,7 +449,7 @@ def source_build_id(extra=""):
     import os
     csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
     names = sorted(["sort.hip", "build.hip", "refine.hip", "nearest.hip", "cutbuild.hip", "rays.hip", "tritri.hip", "geometry.hip",
-                    "sign.hip", "winding.hip", "kbest.hip", "raycast.hip", "raycast_all.hip", "api.cpp", "devmem.cpp", "hostpipe.cpp", "entrycut.cpp", "blob.cpp",
+                    "sign.hip", "winding.hip", "kbest.hip", "raycast.hip", "raycast_all.hip", "within.hip", "api.cpp", "devmem.cpp", "hostpipe.cpp", "entrycut.cpp", "blob.cpp",
                     "hostpipe.h", "hostplan.h", "loaders.cpp", "common.h", "internal.h", "knn.h", "rays.h"])
     h = hashlib.sha256()
     for p in [os.path.join(csrc, n) for n in names] + [os.path.join(csrc, "..", "..", "include", "meshsearch.h")]:

@@ -1562,6 +1562,201 @@ int msh_tree_knearest_stats(msh_tree* t, const double* d_q, size_t S, uint32_t K
     return MSH_OK;
 }
 
+// ---- all primitives within a radius: counts and sorted CSR lists (within.hip) ----
+static const char* const kWithinNeeds = "radius queries need";
+// the scalar radius, checked before the handle as check_kbest_args does (a per-row radius that is negative or NaN is no
+// error: that row is empty)
+static int check_within_radius(double r_max, const double* r_rows, const char* fn) {
+    if (!r_rows && !(r_max >= 0.0)) {
+        set_error("%s: r_max must be >= 0 (+inf: every primitive), got %g", fn, r_max);
+        return MSH_EINVAL;
+    }
+    return MSH_OK;
+}
+
+static int within_count_run(msh_tree* t, const double* d_q, double r_max, const double* d_r, size_t S,
+                            uint32_t* d_count, hipStream_t s) {
+    WsOrder order(t, s);
+    QueryOrder ord;
+    MSH_TRY(sort_queries(t, d_q, nullptr, S, s, &ord, true));
+    return launch_within_count(t, ord, r_max, d_r, S, d_count, s);
+}
+
+static int within_count_device(msh_tree* t, int kind, const double* d_q, size_t S, double r_max, const double* d_r,
+                               uint32_t* d_count, void* stream, const char* fn) {
+    MSH_TRY(check_within_radius(r_max, d_r, fn));
+    MSH_TRY(check_plain_tree(t, kind, fn, kWithinNeeds));
+    MSH_TRY(check_count(S, fn));
+    if (S == 0) return MSH_OK;
+    if (!d_q || !d_count) { set_error("%s: null argument", fn); return MSH_EINVAL; }
+    return within_count_run(t, d_q, r_max, d_r, S, d_count, pick(t, stream));
+}
+
+static int within_count_host(msh_tree* t, int kind, const double* q, size_t S, double r_max, const double* r_rows,
+                             uint32_t* count, const char* fn) {
+    MSH_TRY(check_within_radius(r_max, r_rows, fn));
+    MSH_TRY(check_plain_tree(t, kind, fn, kWithinNeeds));
+    MSH_TRY(check_count(S, fn));
+    if (S == 0) return MSH_OK;
+    if (!q || !count) { set_error("%s: null argument", fn); return MSH_EINVAL; }
+    HostCols c;
+    const auto cq = c.in(q, 3);
+    const auto cr = c.in(r_rows, r_rows ? 1 : 0);
+    const auto ccount = c.out(count, 1);
+    return host_call(t, S, c, kNoCut, [&](msh_tree* h, size_t n, const Slabs& d) {
+        return within_count_run(h, d[cq], r_max, r_rows ? d[cr] : nullptr, n, d[ccount], h->stream);
+    });
+}
+
+int msh_points_within_count(msh_tree* t, const double* q, size_t S, double r_max, const double* r_rows,
+                            uint32_t* count) {
+    return within_count_host(t, kPoints, q, S, r_max, r_rows, count, "msh_points_within_count");
+}
+int msh_points_within_count_device(msh_tree* t, const double* d_q, size_t S, double r_max, const double* d_r_rows,
+                                   uint32_t* d_count, void* stream) {
+    return within_count_device(t, kPoints, d_q, S, r_max, d_r_rows, d_count, stream, "msh_points_within_count_device");
+}
+int msh_tree_within_count(msh_tree* t, const double* q, size_t S, double r_max, const double* r_rows, uint32_t* count) {
+    return within_count_host(t, kTriangles, q, S, r_max, r_rows, count, "msh_tree_within_count");
+}
+int msh_tree_within_count_device(msh_tree* t, const double* d_q, size_t S, double r_max, const double* d_r_rows,
+                                 uint32_t* d_count, void* stream) {
+    return within_count_device(t, kTriangles, d_q, S, r_max, d_r_rows, d_count, stream, "msh_tree_within_count_device");
+}
+
+// raycast_all_run's shape: count, read K back, then scan / fill / order / emit the first min(K, cap) entries.  host_out:
+// the outputs are host arrays -- the list comes through device buffers of its own and the call returns after the
+// download; otherwise they are device arrays and everything after the read-back of K is left queued on s.
+static int within_run(msh_tree* t, const double* d_q, double r_max, const double* d_r, size_t S, bool host_out,
+                      uint32_t* counts, const WithinOut& out, size_t cap, size_t* K, hipStream_t s, const char* fn) {
+    DevBuf did, ddist, dpt, dpart;
+    int st = MSH_OK;
+    do {
+        WsOrder order(t, s);
+        QueryOrder ord;
+        if ((st = sort_queries(t, d_q, nullptr, S, s, &ord, true)) != MSH_OK) break;
+        HitTotals tot{};
+        if ((st = launch_within_all_count(t, ord, r_max, d_r, S, &tot, s)) != MSH_OK) break;
+        // the 64-bit sum is the detector: the 32-bit scan below is never run on counts it would wrap on
+        if (tot.K > 0xFFFFFFFFull) {
+            set_error("%s: %llu entries exceed the 32-bit offset range of one call (split the rows)", fn,
+                      (unsigned long long)tot.K);
+            st = MSH_EINVAL;
+            break;
+        }
+        *K = (size_t)tot.K;
+        const size_t n = std::min<size_t>((size_t)tot.K, cap);
+        WithinOut d = out;
+        if (host_out && n) {
+            if ((st = did.reserve(n * sizeof(uint32_t))) != MSH_OK) break;
+            if ((st = ddist.reserve(n * sizeof(double))) != MSH_OK) break;
+            if (out.pt && (st = dpt.reserve(3 * n * sizeof(double))) != MSH_OK) break;
+            if (out.part && (st = dpart.reserve(n * sizeof(uint32_t))) != MSH_OK) break;
+            d = WithinOut{did.as<uint32_t>(), ddist.as<double>(), out.pt ? dpt.as<double>() : nullptr,
+                          out.part ? dpart.as<uint32_t>() : nullptr};
+        }
+        if ((st = launch_within_emit(t, ord, r_max, d_r, S, tot, d, n, s)) != MSH_OK) break;
+        hipError_t e = hipSuccess;
+        const hipMemcpyKind kind = host_out ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        if (counts) e = hipMemcpyAsync(counts, t->ws.flags.ptr, S * sizeof(uint32_t), kind, s);
+        if (host_out && n) {
+            if (e == hipSuccess) e = hipMemcpyAsync(out.id, d.id, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(out.dist, d.dist, n * sizeof(double), hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess && out.pt)
+                e = hipMemcpyAsync(out.pt, d.pt, 3 * n * sizeof(double), hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess && out.part)
+                e = hipMemcpyAsync(out.part, d.part, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+        }
+        if (e == hipSuccess && host_out) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            set_error("%s: %s", fn, hipGetErrorString(e));
+            st = MSH_EDEVICE;
+        }
+    } while (0);
+    if (host_out || st != MSH_OK) (void)hipStreamSynchronize(s);
+    did.release(); ddist.release(); dpt.release(); dpart.release();
+    return st;
+}
+
+static int check_within(msh_tree* t, int kind, double r_max, const double* r_rows, size_t S, const uint32_t* id,
+                        const double* dist, size_t cap, size_t* K, const char* fn) {
+    MSH_TRY(check_within_radius(r_max, r_rows, fn));
+    MSH_TRY(check_plain_tree(t, kind, fn, kWithinNeeds));
+    MSH_TRY(check_count(S, fn));
+    if (!K || (cap && (!id || !dist))) {
+        set_error("%s: null argument", fn);
+        return MSH_EINVAL;
+    }
+    *K = 0;
+    return MSH_OK;
+}
+
+static int within_device(msh_tree* t, int kind, const double* d_q, size_t S, double r_max, const double* d_r,
+                         uint32_t* d_counts, const WithinOut& o, size_t cap, size_t* K, void* stream, const char* fn) {
+    MSH_TRY(check_within(t, kind, r_max, d_r, S, o.id, o.dist, cap, K, fn));
+    if (S == 0) return MSH_OK;
+    if (!d_q) { set_error("%s: null argument", fn); return MSH_EINVAL; }
+    return within_run(t, d_q, r_max, d_r, S, false, d_counts, o, cap, K, pick(t, stream), fn);
+}
+
+static int within_host(msh_tree* t, int kind, const double* q, size_t S, double r_max, const double* r_rows,
+                       uint32_t* counts, const WithinOut& o, size_t cap, size_t* K, const char* fn) {
+    MSH_TRY(check_within(t, kind, r_max, r_rows, S, o.id, o.dist, cap, K, fn));
+    if (S == 0) return MSH_OK;
+    if (!q) { set_error("%s: null argument", fn); return MSH_EINVAL; }
+    // the list stays on the handle's own device, as the all-hits lists do: the rows are uploaded whole
+    hipStream_t s = t->stream;
+    DevBuf dq, dr;
+    int st = upload(dq, q, 3 * S, s);
+    if (st == MSH_OK && r_rows) st = upload(dr, r_rows, S, s);
+    if (st == MSH_OK)
+        st = within_run(t, dq.as<double>(), r_max, r_rows ? dr.as<double>() : nullptr, S, true, counts, o, cap, K, s, fn);
+    (void)hipStreamSynchronize(s);
+    dq.release(); dr.release();
+    return st;
+}
+
+int msh_points_within(msh_tree* t, const double* q, size_t S, double r_max, const double* r_rows, uint32_t* counts,
+                      uint32_t* idx, double* dist, size_t cap, size_t* K) {
+    return within_host(t, kPoints, q, S, r_max, r_rows, counts, WithinOut{idx, dist, nullptr, nullptr}, cap, K,
+                       "msh_points_within");
+}
+int msh_points_within_device(msh_tree* t, const double* d_q, size_t S, double r_max, const double* d_r_rows,
+                             uint32_t* d_counts, uint32_t* d_idx, double* d_dist, size_t cap, size_t* K, void* stream) {
+    return within_device(t, kPoints, d_q, S, r_max, d_r_rows, d_counts, WithinOut{d_idx, d_dist, nullptr, nullptr}, cap,
+                         K, stream, "msh_points_within_device");
+}
+int msh_tree_within(msh_tree* t, const double* q, size_t S, double r_max, const double* r_rows, uint32_t* counts,
+                    uint32_t* face, double* dist, double* pt, uint32_t* part, size_t cap, size_t* K) {
+    return within_host(t, kTriangles, q, S, r_max, r_rows, counts, WithinOut{face, dist, pt, part}, cap, K,
+                       "msh_tree_within");
+}
+int msh_tree_within_device(msh_tree* t, const double* d_q, size_t S, double r_max, const double* d_r_rows,
+                           uint32_t* d_counts, uint32_t* d_face, double* d_dist, double* d_pt, uint32_t* d_part,
+                           size_t cap, size_t* K, void* stream) {
+    return within_device(t, kTriangles, d_q, S, r_max, d_r_rows, d_counts, WithinOut{d_face, d_dist, d_pt, d_part}, cap,
+                         K, stream, "msh_tree_within_device");
+}
+
+int msh_tree_within_stats(msh_tree* t, const double* d_q, size_t S, double r_max, const double* d_r_rows,
+                          uint64_t counts[4]) {
+    const char* fn = "msh_tree_within_stats";
+    MSH_TRY(check_within_radius(r_max, d_r_rows, fn));
+    if (!t) { set_error("%s: null tree handle", fn); return MSH_EINVAL; }
+    MSH_TRY(check_plain_tree(t, t->kind == kPoints ? kPoints : kTriangles, fn, kWithinNeeds));
+    MSH_TRY(check_count(S, fn));
+    if (!counts) { set_error("%s: null argument", fn); return MSH_EINVAL; }
+    for (int k = 0; k < 4; ++k) counts[k] = 0;
+    if (S == 0) return MSH_OK;
+    if (!d_q) { set_error("%s: null argument", fn); return MSH_EINVAL; }
+    unsigned long long h[4] = {0, 0, 0, 0};
+    MSH_TRY(stats_call(t, d_q, nullptr, S, 4, h, 4, [&](const QueryOrder& ord, unsigned long long* d, hipStream_t s) {
+        return launch_within_stats(t, ord, r_max, d_r_rows, S, d, s);
+    }));
+    for (int k = 0; k < 4; ++k) counts[k] = h[k];
+    return MSH_OK;
+}
+
 // ---- mesh geometry ----
 int msh_vertex_normals_device(const double* d_v, size_t P, const uint32_t* d_f, size_t T, double* d_vn, void* stream) {
     if (P && (!d_v || !d_vn)) { set_error("msh_vertex_normals_device: null argument"); return MSH_EINVAL; }

@@ -575,6 +575,18 @@ __host__ __device__ inline unsigned long long allhits_t_key(double t) {
     return u;
 }
 
+// CSR lists (raycast_all.hip, within.hip): the row whose segment holds entry p, the last r with offsets[r] <= p (rows
+// without entries share their successor's offset)
+__device__ inline size_t hit_row(const uint32_t* __restrict__ offsets, size_t S, size_t p) {
+    size_t lo = 0, hi = S;
+    while (lo < hi) {
+        const size_t mid = lo + (hi - lo) / 2;
+        if ((size_t)offsets[mid] <= p) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo - 1;  // offsets[0] = 0 <= p
+}
+
 // Per-lane traversal stack: entry sp lives in LDS (lds[sp * kBlock], lane-interleaved) for
 // sp < kStack and in the block's global spill area beyond.  The spill side uses the nontemporal
 // builtins so the compiler cannot fold the two cases into one generic (flat) access through a

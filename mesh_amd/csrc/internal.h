@@ -358,6 +358,39 @@ int launch_raycast_all_count(msh_tree* tree, const QueryOrder& ord, const double
                              hipStream_t s);
 int launch_raycast_all_emit(msh_tree* tree, const QueryOrder& ord, const double* d_range, size_t S, const HitTotals& tot,
                             const HitOut& o, size_t n_emit, hipStream_t s);
+// The long-row ordering of a CSR list of K entries over S rows (the all-hits lists and the radius lists): on return
+// (*idx)[p] is the entry that comes p-th by (row, d_key by value, d_id).  d_key (K,) is >= 0 and never NaN (its radix
+// key is allhits_t_key), d_id (K,) < 2^id_bits is distinct within a row, d_offsets (S,) the exclusive scan of the
+// counts.  In: *idx a buffer of K words; out: that buffer or ws.vals_alt.  Four stable LSD radix sorts of the index
+// (id, key low, key high, row).  Uses ws.keys, keys_alt, vals_alt, hist, scan.  Asynchronous on s.
+int order_csr_entries(const double* d_key, const uint32_t* d_id, int id_bits, const uint32_t* d_offsets, size_t S,
+                      size_t K, Workspace& ws, uint32_t** idx, hipStream_t s);
+
+// ---- all primitives within a radius (within.hip) ----
+// Row r is (q[r], radius): d_r == nullptr: r_max for every row, else d_r[r] in the caller's row order.  A primitive
+// qualifies when d2 <= radius * radius, d2 the K-nearest queries' exact squared distance (knn.h kb_eval); a row with a
+// non-finite point or a negative or NaN radius has none.  Point trees and plain triangle trees; ord: the rows' slot order
+// (lazy: ord.q are the caller's rows).  Every walk uses ws.spill and is asynchronous on s.
+// d_counts[r] = the number of qualifying primitives; msh_timing_get name "within_count".
+int launch_within_count(msh_tree* tree, const QueryOrder& ord, double r_max, const double* d_r, size_t S,
+                        uint32_t* d_counts, hipStream_t s);
+// the count walk, untimed, nothing written: d_stats[0] += nodes visited, [1] += primitives evaluated, [2] += entries,
+// [3] = max(the deepest stack any row reached)
+int launch_within_stats(msh_tree* tree, const QueryOrder& ord, double r_max, const double* d_r, size_t S,
+                        unsigned long long* d_stats, hipStream_t s);
+// The lists as CSR, sorted by (row, d2, id), in the two steps of the all-hits lists (HitTotals; the same buffers of ws):
+// count into ws.flags and the totals read back on s (synchronous); then scan, fill, order, emit of the first n_emit <= K
+// entries to o (asynchronous).  id and dist (n_emit,); pt (n_emit,3) and part (n_emit,) may be nullptr (triangle trees).
+struct WithinOut {
+    uint32_t* id;
+    double* dist;
+    double* pt;
+    uint32_t* part;
+};
+int launch_within_all_count(msh_tree* tree, const QueryOrder& ord, double r_max, const double* d_r, size_t S,
+                            HitTotals* out, hipStream_t s);
+int launch_within_emit(msh_tree* tree, const QueryOrder& ord, double r_max, const double* d_r, size_t S,
+                       const HitTotals& tot, const WithinOut& o, size_t n_emit, hipStream_t s);
 
 // ---- triangle-triangle (tritri.hip) ----
 constexpr int kLaneSort = 32;  // rows of up to this many hits are ordered by their own lane (k_tritri_all, k_raycast_all)

@@ -49,22 +49,6 @@ struct KbArgs {
     unsigned long long* stats;  // STATS launches: [0] nodes, [1] primitives, [2] insertions, [3] deepest stack
 };
 
-// exact squared distance from q to a leaf, and the leaf's id
-template <bool TRI>
-__device__ inline double kb_eval(const void* __restrict__ leaves, int leaf, const D3& q, uint32_t& id) {
-    if constexpr (TRI) {
-        D3 a, b, c, o;
-        int part;
-        load_tri(static_cast<const TriRec*>(leaves), leaf, a, b, c, id);
-        return closest_on_triangle(q, a, b, c, o, part);
-    } else {
-        const double2* p = reinterpret_cast<const double2*>(static_cast<const PtRec*>(leaves) + leaf);
-        const double2 x0 = p[0], x1 = p[1];
-        id = (uint32_t)__double_as_longlong(x1.y);
-        return sqdist(q, D3{x0.x, x0.y, x1.x});
-    }
-}
-
 // The leaf policy of WalkerT::step.  CAP: 1 the list is (kd2, kid); 8 or 16: LDS columns of stride kBlock;
 // 0: the workspace (ld2 / lid point at this lane's entry 0, stride 64).  (kd2, kid) is the K-th entry once the list is
 // full; until then kd2 = +inf, so only the radius prunes.

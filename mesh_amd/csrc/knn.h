@@ -232,6 +232,23 @@ struct PtPol {
     }
 };
 
+// exact squared distance from q to a leaf of a triangle (TRI) or point tree, and the leaf's id: the d2 of the K-nearest
+// and the radius lists (kbest.hip, within.hip)
+template <bool TRI>
+__device__ inline double kb_eval(const void* __restrict__ leaves, int leaf, const D3& q, uint32_t& id) {
+    if constexpr (TRI) {
+        D3 a, b, c, o;
+        int part;
+        load_tri(static_cast<const TriRec*>(leaves), leaf, a, b, c, id);
+        return closest_on_triangle(q, a, b, c, o, part);
+    } else {
+        const double2* p = reinterpret_cast<const double2*>(static_cast<const PtRec*>(leaves) + leaf);
+        const double2 x0 = p[0], x1 = p[1];
+        id = (uint32_t)__double_as_longlong(x1.y);
+        return sqdist(q, D3{x0.x, x0.y, x1.x});
+    }
+}
+
 // Stack entries (node or ~leaf ref, fp32 bound bits): 8 B, or 4 B for trees of <= 2^20 leaves — the bound's top
 // 11 bits (sign 0, exponent, 2 mantissa bits: the bound truncated, so still a lower bound; a pop it fails to prune
 // only visits a node whose children are then bounded exactly) over the ref's 21 bits, one v_bfi to pack, a v_and

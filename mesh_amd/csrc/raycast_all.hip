@@ -152,17 +152,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
     }
 }
 
-// the row whose segment holds entry p: the last r with offsets[r] <= p (rows without hits share their successor's offset)
-__device__ inline size_t hit_row(const uint32_t* __restrict__ offsets, size_t S, size_t p) {
-    size_t lo = 0, hi = S;
-    while (lo < hi) {
-        const size_t mid = lo + (hi - lo) / 2;
-        if ((size_t)offsets[mid] <= p) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo - 1;  // offsets[0] = 0 <= p
-}
-
 // keys[p] of the entry idx[p] (idx == nullptr: p itself, and idx_out[p] = p) for one of the order's four sorts
 enum { kKeyFace = 0, kKeyTLo = 1, kKeyTHi = 2, kKeyRow = 3 };
 template <int kKey>
@@ -295,11 +284,6 @@ int launch_raycast_all_emit(msh_tree* tree, const QueryOrder& ord, const double*
     MSH_TRY(ws.out_b.reserve(K * sizeof(uint32_t)));
     MSH_TRY(ws.out_c.reserve(K * sizeof(uint32_t)));
     MSH_TRY(ws.out_d.reserve(K * sizeof(uint32_t)));
-    if (!lane_order) {
-        MSH_TRY(ws.keys.reserve(K * sizeof(uint32_t)));
-        MSH_TRY(ws.keys_alt.reserve(K * sizeof(uint32_t)));
-        MSH_TRY(ws.vals_alt.reserve(K * sizeof(uint32_t)));
-    }
     uint32_t* counts = ws.flags.as<uint32_t>();
     uint32_t* offsets = ws.ranges.as<uint32_t>();
     {
@@ -318,28 +302,39 @@ int launch_raycast_all_emit(msh_tree* tree, const QueryOrder& ord, const double*
     a.n_emit = n_emit;
     MSH_TRY(launch_all<kHitFill>(tree, a, s));
     if (!lane_order) {
-        // Long rows: stable sorts of an index over all K entries, least significant key first, leave it sorted by
-        // (row, t, face) in time linear in K however long a row is.
         TimedLaunch tl("raycast_order", s);
-        uint32_t *keys = ws.keys.as<uint32_t>(), *keys_alt = ws.keys_alt.as<uint32_t>(), *idx_alt = ws.vals_alt.as<uint32_t>();
-        const unsigned nb = blocks_for(K);
-        const int bits[4] = {bits_for(tree->T), 32, 32, bits_for(S)};
-        for (int pass = 0; pass < 4; ++pass) {
-            const uint32_t* in = pass ? idx : nullptr;
-            if (pass == kKeyFace) k_hit_keys<kKeyFace><<<nb, kBlock, 0, s>>>(in, K, a.ht, a.hf, offsets, S, keys, idx);
-            else if (pass == kKeyTLo) k_hit_keys<kKeyTLo><<<nb, kBlock, 0, s>>>(in, K, a.ht, a.hf, offsets, S, keys, idx);
-            else if (pass == kKeyTHi) k_hit_keys<kKeyTHi><<<nb, kBlock, 0, s>>>(in, K, a.ht, a.hf, offsets, S, keys, idx);
-            else k_hit_keys<kKeyRow><<<nb, kBlock, 0, s>>>(in, K, a.ht, a.hf, offsets, S, keys, idx);
-            MSH_HIP(hipGetLastError());
-            bool alt = false;
-            MSH_TRY(radix_sort_pairs(keys, idx, keys_alt, idx_alt, K, bits[pass], ws, s, 0, &alt));
-            if (alt) { std::swap(keys, keys_alt); std::swap(idx, idx_alt); }
-        }
+        MSH_TRY(order_csr_entries(a.ht, a.hf, bits_for(tree->T), offsets, S, K, ws, &idx, s));
     }
     EmitArgs e{a.tris, a.o, a.d, d_range, S, offsets, idx, a.ht, a.hl, n_emit, o.t, o.face, o.pt, o.side};
     TimedLaunch tl("raycast_emit", s);
     k_hit_emit<<<blocks_for(n_emit), kBlock, 0, s>>>(e);
     MSH_HIP(hipGetLastError());
+    return MSH_OK;
+}
+
+// Long rows: stable sorts of an index over all K entries, least significant key first, leave it sorted by
+// (row, key by value, id) in time linear in K however long a row is (internal.h order_csr_entries).
+int order_csr_entries(const double* d_key, const uint32_t* d_id, int id_bits, const uint32_t* d_offsets, size_t S,
+                      size_t K, Workspace& ws, uint32_t** idx_io, hipStream_t s) {
+    MSH_TRY(ws.keys.reserve(K * sizeof(uint32_t)));
+    MSH_TRY(ws.keys_alt.reserve(K * sizeof(uint32_t)));
+    MSH_TRY(ws.vals_alt.reserve(K * sizeof(uint32_t)));
+    uint32_t *keys = ws.keys.as<uint32_t>(), *keys_alt = ws.keys_alt.as<uint32_t>(), *idx_alt = ws.vals_alt.as<uint32_t>();
+    uint32_t* idx = *idx_io;
+    const unsigned nb = blocks_for(K);
+    const int bits[4] = {id_bits, 32, 32, bits_for(S)};
+    for (int pass = 0; pass < 4; ++pass) {
+        const uint32_t* in = pass ? idx : nullptr;
+        if (pass == kKeyFace) k_hit_keys<kKeyFace><<<nb, kBlock, 0, s>>>(in, K, d_key, d_id, d_offsets, S, keys, idx);
+        else if (pass == kKeyTLo) k_hit_keys<kKeyTLo><<<nb, kBlock, 0, s>>>(in, K, d_key, d_id, d_offsets, S, keys, idx);
+        else if (pass == kKeyTHi) k_hit_keys<kKeyTHi><<<nb, kBlock, 0, s>>>(in, K, d_key, d_id, d_offsets, S, keys, idx);
+        else k_hit_keys<kKeyRow><<<nb, kBlock, 0, s>>>(in, K, d_key, d_id, d_offsets, S, keys, idx);
+        MSH_HIP(hipGetLastError());
+        bool alt = false;
+        MSH_TRY(radix_sort_pairs(keys, idx, keys_alt, idx_alt, K, bits[pass], ws, s, 0, &alt));
+        if (alt) { std::swap(keys, keys_alt); std::swap(idx, idx_alt); }
+    }
+    *idx_io = idx;
     return MSH_OK;
 }
 

@@ -189,6 +189,18 @@ class Mesh(object):
         use the entry cut, so none is asked for)."""
         return self.compute_aabb_tree().nearest_k(vertices, k, max_distance)
 
+    def vertices_within(self, vertices, r):
+        """(counts (S,) uint32, indices (K,) intp, distances (K,)): every vertex of this mesh within `r` (a scalar or
+        (S,)) of every row of `vertices`, as CSR, nearest first (search.ClosestPointTree.within on a tree built for
+        this call)."""
+        return search.ClosestPointTree(self).within(vertices, r)
+
+    def faces_within(self, vertices, r, points=False):
+        """(counts (S,) uint32, faces (K,) uint32, distances (K,)[, points (K,3)]): every face of this mesh within `r`
+        (a scalar or (S,)) of every row of `vertices`, as CSR sorted by (row, distance, face) (search.AabbTree.within on
+        a tree built for this call; the walk does not use the entry cut, so none is asked for)."""
+        return self.compute_aabb_tree().within(vertices, r, points)
+
     def ray_cast(self, origins, directions, t_range=None, barycentric=False):
         """(t (S,), faces (S,) uint32, points (S,3)) of the first hit of every ray `origins[i] + t directions[i]` with
         this mesh, t in `t_range`; with `barycentric` also the weights (S,3) (search.AabbTree.ray_cast on a tree built

@@ -56,6 +56,20 @@ class AabbTree(object):
             return faces, parts, pts, dist
         return faces, pts, dist
 
+    def within(self, v_samples, r, points=False, parts=False):
+        """Every face within ``r`` of each sample, as CSR: (counts (S,) u32, faces (K,) u32, distances (K,) f64), with
+        ``points=True`` also the closest points (K,3) f64 and with ``parts=True`` their part codes (K,) u32.  The
+        exclusive scan of ``counts`` indexes the lists; a row's faces are sorted by (squared distance, face id), so its
+        first ``k`` entries are ``nearest_k``'s and no row is truncated.  ``r`` is a scalar or (S,); ``r = inf`` lists
+        every face."""
+        from . import spatialsearch
+        return spatialsearch.aabbtree_within(self.cpp_handle, _f64c(v_samples), r, points, parts)
+
+    def count_within(self, v_samples, r):
+        """uint32 (S,): how many faces lie within ``r`` (a scalar or (S,)) of each sample (see ``within``)."""
+        from . import spatialsearch
+        return spatialsearch.aabbtree_within_count(self.cpp_handle, _f64c(v_samples), r)
+
     def nearest_alongnormal(self, points, normals):
         """Nearest hit of the lines through ``points`` along +/-``normals``: (dist, face, point)."""
         from . import spatialsearch
@@ -230,6 +244,59 @@ class ClosestPointTree(object):
         if single:
             dist, ind = dist[0], ind[0]
         return dist, ind
+
+    def within(self, x, r):
+        """Every vertex within ``r`` of each sample, as CSR: (counts (S,) u32, indices (K,) intp, distances (K,) f64);
+        the exclusive scan of ``counts`` indexes the lists, and a row's neighbours come nearest first, ties by vertex
+        index.  ``r`` is a scalar or (S,).  No row is truncated: the first ``k`` entries of a row are ``query``'s."""
+        from . import spatialsearch
+        counts, idx, dist = spatialsearch.points_within(self._h, _f64c(x).reshape(-1, 3), r)
+        return counts, idx.astype(np.intp), dist
+
+    def query_ball_point(self, x, r, p=2.0, eps=0, workers=1, return_sorted=None, return_length=False):
+        """``scipy.spatial.KDTree.query_ball_point(x, r, ...)`` on the GPU: the indices of all vertices within ``r`` of
+        each sample (``d2 <= r * r`` with the exact squared distance of ``query``).  A single (3,) point gives a list
+        of indices (or their number with ``return_length``); (..., 3) input gives an object array of lists (or an intp
+        array of lengths) of the leading shape.  ``r`` is broadcast against the samples.  ``return_sorted`` True, or
+        None on multi-point input, sorts each list ascending by index; False keeps the lists nearest first, ties by
+        index.  Only the Euclidean metric without approximation is supported: ``p != 2`` or ``eps != 0`` raise
+        ValueError; ``workers`` is accepted and ignored."""
+        from . import spatialsearch
+        if float(p) != 2.0:
+            raise ValueError("query_ball_point: only p = 2 (the Euclidean metric) is supported, got %r" % (p,))
+        if float(eps) != 0.0:
+            raise ValueError("query_ball_point: only eps = 0 (no approximation) is supported, got %r" % (eps,))
+        q = _f64c(x)
+        if q.ndim < 1 or q.shape[-1] != 3:
+            raise ValueError("query_ball_point: x must have shape (..., 3), got %r" % (q.shape,))
+        lead = q.shape[:-1]
+        q = q.reshape(-1, 3)
+        S = q.shape[0]
+        rr = np.asarray(r, dtype=np.float64)
+        if rr.ndim:
+            try:
+                rr = np.ascontiguousarray(np.broadcast_to(rr, lead)).reshape(-1)
+            except ValueError:
+                raise ValueError("query_ball_point: r of shape %r does not broadcast against the %r samples" %
+                                 (np.shape(r), lead))
+        if return_length:
+            n = spatialsearch.points_within_count(self._h, q, rr).astype(np.intp)
+            return int(n[0]) if not lead else n.reshape(lead)
+        counts, idx, _ = spatialsearch.points_within(self._h, q, rr)
+        idx = idx.astype(np.intp)
+        if return_sorted or (return_sorted is None and lead):
+            # one segmented sort over the CSR: by row, then by index
+            idx = idx[np.lexsort((idx, np.repeat(np.arange(S), counts)))]
+        flat = idx.tolist()
+        if not lead:
+            return flat
+        ends = np.cumsum(counts, dtype=np.int64).tolist()
+        out = np.empty(S, dtype=object)
+        a = 0
+        for i, b in enumerate(ends):
+            out[i] = flat[a:b]
+            a = b
+        return out.reshape(lead)
 
     def nearest(self, v_samples):
         # same container types as the reference's zip(*[...]) over per-sample KDTree queries

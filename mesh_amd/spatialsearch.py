@@ -14,7 +14,9 @@ hits which face, as a sorted (K, 2) pair list; ``aabbtree_signed_distance`` and 
 inside / outside, the first on closed manifold meshes, the second on any triangle set; ``aabbtree_nearest_k`` and
 ``points_nearest_k`` return the K nearest faces or points of every row, optionally within a radius;
 ``aabbtree_raycast`` and ``aabbtree_occluded`` answer first-hit and occlusion queries for arbitrary rays,
-``aabbtree_raycast_count`` and ``aabbtree_raycast_all`` return how many faces each ray meets and all of them in order.
+``aabbtree_raycast_count`` and ``aabbtree_raycast_all`` return how many faces each ray meets and all of them in order;
+``aabbtree_within`` / ``points_within`` and their ``_count`` forms return every face or point within a radius of every
+row, untruncated, as CSR lists or per-row counts.
 """
 import numpy as np
 
@@ -166,6 +168,92 @@ def points_nearest_k(tree, q, k, max_distance=np.inf):
     idx, dist, count = N.empty_results(((S, k), np.uint32), ((S, k), np.float64), ((S,), np.uint32))
     N.check(N.lib().msh_points_knearest(tree.ptr, N.dptr(q), S, k, r, N.uptr(idx), N.dptr(dist), N.uptr(count)))
     return idx, dist, count
+
+
+def _within_args(tree, q, r, fn, kind):
+    """The validated arguments of a radius query: (q (S,3) float64 C order, r_max, r_rows or None)."""
+    if not isinstance(tree, N.Handle) or tree.ptr is None:
+        raise TypeError("%s: expected a tree handle" % fn)
+    if not isinstance(q, np.ndarray):
+        raise TypeError("%s() argument 2 must be numpy.ndarray" % fn)
+    if q.ndim != 2 or q.shape[1] != 3:
+        raise ValueError("Input must be Nx3")
+    if tree.kind != kind:
+        raise TypeError("%s: handle is not a %s tree" % (fn, "point" if kind == "points" else "triangle"))
+    r_max, r_rows = N.check_within(r, q.shape[0], fn)
+    return np.ascontiguousarray(q, dtype=np.float64), r_max, r_rows
+
+
+def _within_call(S, specs, call):
+    """The list form of a radius query: one call with a first guess at the capacity, a second with cap = K only when
+    K > cap (as ``_pairs_call``) -> (counts (S,) uint32, the owned (K, ...) arrays of ``specs``; None where a spec is
+    None).  ``call(counts, out, cap, K)`` returns the status."""
+    counts = np.empty(S, dtype=np.uint32)
+    K = N._sz(0)
+
+    def run(cap):
+        out = [None if sp is None else np.empty((cap,) + sp[0], dtype=sp[1]) for sp in specs]
+        N.check(call(counts, out, cap, K))
+        return out
+
+    cap = _first_cap(S)
+    out = run(cap)
+    if K.value > cap:
+        out = run(K.value)
+    return (counts,) + tuple(x[:K.value].copy() for x in out if x is not None)
+
+
+def points_within_count(tree, q, r):
+    """counts (S,) uint32: how many points of a point tree lie within ``r`` of every row of ``q`` (``d2 <= r * r`` with
+    the exact squared distance of ``points_nearest_k``).  ``r`` is a scalar (negative or NaN: ValueError) or an (S,)
+    array (a negative or NaN entry, like a non-finite row, counts 0)."""
+    q, r_max, r_rows = _within_args(tree, q, r, "points_within_count", "points")
+    S = q.shape[0]
+    counts, = N.empty_results(((S,), np.uint32))
+    N.check(N.lib().msh_points_within_count(tree.ptr, N.dptr(q), S, r_max, N.dptr(r_rows), N.uptr(counts)))
+    return counts
+
+
+def points_within(tree, q, r):
+    """(counts (S,) uint32, idx (K,) uint32, dist (K,) float64): every point of a point tree within ``r`` of every row
+    of ``q``, as CSR -- the exclusive scan of ``counts`` indexes the lists -- sorted by (row, squared distance, point
+    index).  No row is truncated: the first ``k`` entries of a row are ``points_nearest_k(tree, q, k, r)``'s, bit for
+    bit.  ``r`` as for ``points_within_count``; ``r = inf`` lists every point.
+    ``search.ClosestPointTree.query_ball_point`` is its scipy-shaped form."""
+    q, r_max, r_rows = _within_args(tree, q, r, "points_within", "points")
+    S = q.shape[0]
+    fn = N.lib().msh_points_within
+    return _within_call(S, [((), np.uint32), ((), np.float64)],
+                        lambda counts, out, cap, K: fn(tree.ptr, N.dptr(q), S, r_max, N.dptr(r_rows), N.uptr(counts),
+                                                       N.uptr(out[0]), N.dptr(out[1]), cap, N.ctypes.byref(K)))
+
+
+def aabbtree_within_count(tree, q, r):
+    """counts (S,) uint32: how many faces lie within ``r`` of every row of ``q`` (``d2 <= r * r`` with the exact squared
+    distance ``aabbtree_nearest`` computes; the extra faces of a tree built with them are included).  ``r`` is a scalar
+    (negative or NaN: ValueError) or an (S,) array (a negative or NaN entry, like a non-finite row, counts 0)."""
+    q, r_max, r_rows = _within_args(tree, q, r, "aabbtree_within_count", "triangles")
+    S = q.shape[0]
+    counts, = N.empty_results(((S,), np.uint32))
+    N.check(N.lib().msh_tree_within_count(tree.ptr, N.dptr(q), S, r_max, N.dptr(r_rows), N.uptr(counts)))
+    return counts
+
+
+def aabbtree_within(tree, q, r, points=False, parts=False):
+    """(counts (S,) uint32, face (K,) uint32, dist (K,) float64[, point (K,3) float64][, part (K,) uint32]): every face
+    within ``r`` of every row of ``q``, as CSR -- the exclusive scan of ``counts`` indexes the lists -- sorted by (row,
+    squared distance, face id) (no reference counterpart).  No row is truncated: the first ``k`` entries of a row are
+    ``aabbtree_nearest_k(tree, q, k, r)``'s face, dist, point and part, bit for bit, and with ``r = inf`` entry 0 is
+    ``aabbtree_nearest``'s.  ``r`` as for ``aabbtree_within_count``."""
+    q, r_max, r_rows = _within_args(tree, q, r, "aabbtree_within", "triangles")
+    S = q.shape[0]
+    fn = N.lib().msh_tree_within
+    specs = [((), np.uint32), ((), np.float64), ((3,), np.float64) if points else None,
+             ((), np.uint32) if parts else None]
+    return _within_call(S, specs,
+                        lambda counts, out, cap, K: fn(tree.ptr, N.dptr(q), S, r_max, N.dptr(r_rows), N.uptr(counts),
+                                                       N.uptr(out[0]), N.dptr(out[1]), N.dptr(out[2]), N.uptr(out[3]),
+                                                       cap, N.ctypes.byref(K)))
 
 
 def aabbtree_nearest_barycentric(tree, q):
